@@ -1,8 +1,12 @@
 """Benchmark: batched LZ4 block codec on MI355X (BASELINE.json configs 2 and 3).
 
 One "step" = one pass of the hot path over one batch: decompress of
-1,048,576 x 64 KiB device-resident blocks (config 2, the headline `value`),
-plus the compress pass of the same batch (config 3) reported beside it.
+1,048,576 x 64 KiB device-resident blocks (config 2, the headline `value`).
+A plain run builds that batch, warms up, times `--steps` decodes, checks the
+output and prints the result line; `--dump-outputs DIR` also writes what the
+last step returned.  `--full` adds every other leg beside it: the compress
+pass of the same batch (config 3), the mid-size, random and end-to-end
+decodes, configs 5, 4 and 1 and the CPU baselines.
 
 Data: the Silesia corpus is not available offline, so a seeded synthetic
 "silesia-like" mix (lz4/_synth.py) stands in.  A pool of unique blocks is
@@ -392,6 +396,32 @@ def config1(n_blocks: int, dev) -> dict:
     return res
 
 
+DUMP_BLOCKS = 128   # decoded blocks written out whole by --dump-outputs
+
+
+def dump_outputs(path: str, dst: torch.Tensor, status: torch.Tensor, n: int) -> None:
+    """What the last timed launch_decompress returned, as .npy files under
+    `path` (44 MiB at the default size): status.npy, the n per-block statuses
+    (float32, exact); block_sums.npy, the sum of the decoded bytes of every
+    block (float64, exact), which covers the whole output; blocks_sample.npy,
+    min(DUMP_BLOCKS, n) decoded blocks whole (float32, one row each), a fixed
+    seeded choice whose block numbers are in sample_index.npy (float64).  The
+    inputs are seeded, so two builds run with the same arguments write files
+    that compare array for array."""
+    os.makedirs(path, exist_ok=True)
+    rows = dst.view(n, BLOCK)
+    idx = np.sort(np.random.default_rng(20260).choice(n, size=min(DUMP_BLOCKS, n), replace=False))
+    sample = rows[torch.from_numpy(idx).to(dst.device)].to(torch.float32)
+    sums = torch.empty(n, dtype=torch.float64, device=dst.device)
+    chunk = 8192   # the sum widens its input first: 2 GiB of int32 per chunk
+    for lo in range(0, n, chunk):
+        sums[lo:lo + chunk] = rows[lo:lo + chunk].sum(dim=1, dtype=torch.int32)
+    np.save(os.path.join(path, "status.npy"), status.to(torch.float32).cpu().numpy())
+    np.save(os.path.join(path, "block_sums.npy"), sums.cpu().numpy())
+    np.save(os.path.join(path, "blocks_sample.npy"), sample.cpu().numpy())
+    np.save(os.path.join(path, "sample_index.npy"), idx.astype(np.float64))
+
+
 def decoder_src_sha() -> str:
     """Identity of the decoder kernels that profiles/pmc_decompress.json
     must have been measured on (roofline.traffic is reported only on a match)."""
@@ -409,6 +439,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--blocks", type=int, default=1 << 20, help="64 KiB blocks per GPU (config 2: 1M)")
     ap.add_argument("--pool", type=int, default=4096, help="unique host-generated blocks per rank")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: config 3's compressors, the mid-size, random and "
+                         "end-to-end decodes, the device copy, configs 5, 4 and 1 and the CPU baselines (the options "
+                         "below size or skip those legs); without it only the headline decode is set up and timed")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last decode step returned (see dump_outputs) as DIR/*.npy")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-compress", action="store_true")
     ap.add_argument("--random-blocks", type=int, default=1 << 17, help="blocks of the random-data extra line")
@@ -425,6 +461,8 @@ def main():
     ap.add_argument("--c1-blocks", type=int, default=1000,
                     help="config 1: random 64 KiB blocks through the per-call lz4.block API; 0 = skip")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     world_env = os.environ.get("WORLD_SIZE")
     if world_env is None and args.gpus > 1:
@@ -469,7 +507,7 @@ def main():
         N.launch_compress(src, src_off, src_len, slots, slot_off, slot_cap, out_len, n, N.PARSE_PARALLEL, 1)
 
     c3 = {}
-    if not args.no_compress:
+    if args.full and not args.no_compress:
         c_wall, c_ev = time_kernel(do_pcompress, max(1, args.steps // 2), 1, world)
         assert int((out_len <= 0).sum()) == 0, "parallel compress failed on some block"
         par_total = int(out_len.to(torch.int64).sum())
@@ -510,7 +548,7 @@ def main():
     c_off = offs[:n].clone()
     c_len = out_len.clone()
     comp_sample = None
-    if runs_cpu_baseline(rank, args.no_cpu):   # cpu_baseline at every N (rank 0, after the timed regions)
+    if args.full and runs_cpu_baseline(rank, args.no_cpu):   # cpu_baseline at every N (rank 0, after the timed regions)
         k = min(n, 16384)
         comp_host_np = comp[: int(offs[k])].cpu().numpy()
         oh = offs[: k + 1].cpu().numpy()
@@ -529,7 +567,63 @@ def main():
     if not (ok_status and ok_bytes):
         raise SystemExit(f"decompress verification failed: status_ok={ok_status} bytes_ok={ok_bytes}")
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dst, status, n)
+
     extra = {}
+    # ---- report ----
+    d_step = d_wall / args.steps
+    value = aggregate_gib_s(world, n, BLOCK, d_wall, args.steps)
+    algo_bytes = comp_total + n * BLOCK          # per launch: read compressed + write decoded
+    achieved = algo_bytes / d_ev / 1e9           # GB/s, from HIP events on the launch stream
+    # HBM bytes per launch of the decoder from the committed PMC summary of
+    # this same command (tools/pmc_bench.sh -> profiles/pmc_decompress.json),
+    # used only when it was measured on this configuration
+    traffic = None
+    pmc_path = os.path.join(ROOT, "profiles", "pmc_decompress.json")
+    if os.path.exists(pmc_path):
+        try:
+            with open(pmc_path) as f:
+                pmc = json.load(f)
+            if (pmc.get("blocks") == n and pmc.get("pool") == args.pool
+                    and pmc.get("decoder_src_sha") == decoder_src_sha()):
+                traffic = pmc.get("hbm_bytes_per_launch")
+        except (OSError, ValueError):
+            traffic = None
+    res = {
+        "metric": "GiB/s uncompressed, device-resident, 64 KiB blocks (decompress; compress)",
+        "value": round(value, 2),
+        "unit": "GiB/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(d_step * 1e3, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u8",
+        "data": "synthetic (silesia-like mix, lz4/_synth.py; Silesia unavailable offline)",
+        "config": {"workload": "config 2: decompress 1M x 64 KiB blocks, device-resident, LZ4_compress_default input",
+                   "blocks_per_gpu": n, "block_size": BLOCK, "ratio": round(ratio, 4),
+                   "parallelism": f"shard{world}"},
+        "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic},
+        "decompress_kernel_ms": round(d_ev * 1e3, 3),
+        "decompress_read_gbs": round(comp_total / d_ev / 1e9, 1),
+        "compress": c3,
+        "extra": extra,
+    }
+
+    def finish():
+        if rank == 0:
+            print(json.dumps(res), flush=True)
+        if world > 1:
+            torch.distributed.destroy_process_group()
+
+    if not args.full:
+        # a plain run ends here: the headline is timed, checked and reported
+        return finish()
+
     # ---- extra: a mid-size batch of the same blocks (65 536), which goes to the
     # a mid-size batch through the default dispatch (the row decoder from 32 768 blocks)
     nm = min(65536, n)
@@ -720,55 +814,10 @@ def main():
         extra["config1"] = config1(args.c1_blocks, dev)
         log("[bench] config 1 done")
 
-    # ---- report ----
-    d_step = d_wall / args.steps
-    value = aggregate_gib_s(world, n, BLOCK, d_wall, args.steps)
-    algo_bytes = comp_total + n * BLOCK          # per launch: read compressed + write decoded
-    achieved = algo_bytes / d_ev / 1e9           # GB/s, from HIP events on the launch stream
-    # HBM bytes per launch of the decoder from the committed PMC summary of
-    # this same command (tools/pmc_bench.sh -> profiles/pmc_decompress.json),
-    # used only when it was measured on this configuration
-    traffic = None
-    pmc_path = os.path.join(ROOT, "profiles", "pmc_decompress.json")
-    if os.path.exists(pmc_path):
-        try:
-            with open(pmc_path) as f:
-                pmc = json.load(f)
-            if (pmc.get("blocks") == n and pmc.get("pool") == args.pool
-                    and pmc.get("decoder_src_sha") == decoder_src_sha()):
-                traffic = pmc.get("hbm_bytes_per_launch")
-        except (OSError, ValueError):
-            traffic = None
-    res = {
-        "metric": "GiB/s uncompressed, device-resident, 64 KiB blocks (decompress; compress)",
-        "value": round(value, 2),
-        "unit": "GiB/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(d_step * 1e3, 3),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "u8",
-        "data": "synthetic (silesia-like mix, lz4/_synth.py; Silesia unavailable offline)",
-        "config": {"workload": "config 2: decompress 1M x 64 KiB blocks, device-resident, LZ4_compress_default input",
-                   "blocks_per_gpu": n, "block_size": BLOCK, "ratio": round(ratio, 4),
-                   "parallelism": f"shard{world}"},
-        "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic},
-        "decompress_kernel_ms": round(d_ev * 1e3, 3),
-        "decompress_read_gbs": round(comp_total / d_ev / 1e9, 1),
-        "compress": c3,
-        "extra": extra,
-    }
     if comp_sample is not None:
         host_blocks = src[: len(comp_sample) * BLOCK].view(-1, BLOCK).cpu().numpy()
         res["cpu_baseline"] = cpu_baseline(host_blocks, comp_sample)
-    if rank == 0:
-        print(json.dumps(res), flush=True)
-    if world > 1:
-        torch.distributed.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

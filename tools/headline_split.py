@@ -20,6 +20,6 @@ for i, n in enumerate(short):
         out.append({"parse_ms": round(dur[p], 3), "exec_ms": round(dur[i], 3), "finisher_ms": round(dur[f], 3),
                     "launch_span_ms": round(span, 3)})
 avg = {k: round(sum(o[k] for o in out) / len(out), 3) for k in out[0]} if out else {}
-json.dump({"source": "rocprofv3 --kernel-trace --stats -- python3 bench.py (default args)",
+json.dump({"source": "rocprofv3 --kernel-trace --stats -- python3 bench.py --full",
            "launches": out, "average": avg}, sys.stdout, indent=1)
 print()

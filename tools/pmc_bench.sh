@@ -7,7 +7,7 @@ OUT=$(realpath -m "$1")
 REPO=$(cd "$(dirname "$0")/.." && pwd)
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-ARGS="--steps 1 --warmup 0 --no-cpu --no-compress --e2e-blocks 0 --frame-gib 0 --random-blocks 131072 --c5-total 0 --c1-blocks 0"
+ARGS="--full --steps 1 --warmup 0 --no-cpu --no-compress --e2e-blocks 0 --frame-gib 0 --random-blocks 131072 --c5-total 0 --c1-blocks 0"
 # the decoder's kernels: the row decoder's parse, execution and finisher
 KRX=${KRX:-"rows_parse_kernel|rows_exec_kernel|decompress_kernel<false, true>"}
 i=0

@@ -2,7 +2,7 @@
 
 One decoder launch = the row decoder's three kernels (parse, execution,
 finisher); the k-th dispatch of each kernel belongs to launch k.  Launch
-order in `bench.py --steps 1 --warmup 0 --no-compress`: launch 0 is the
+order in `bench.py --full --steps 1 --warmup 0 --no-compress`: launch 0 is the
 silesia-like headline launch (config 2), then the 65 536-block mid-batch
 launches, and the LAST launch is a random-data launch, whose bytes are known
 (pure streaming: read ~= compressed size, write = decoded size) and serves as

@@ -13,7 +13,7 @@ for r in rows:
     name = r["Kernel_Name"]
     ms = (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6
     by[name].append(round(ms, 3))
-out = {"source": "rocprofv3 --kernel-trace --stats -- python3 bench.py (default args)"}
+out = {"source": "rocprofv3 --kernel-trace --stats -- python3 bench.py --full"}
 for name, ds in by.items():
     short = name.split("(")[0].replace("void ", "").replace("lz4m::", "")
     if not any(k in short for k in ("decompress", "compress", "xxh32")):
