@@ -144,6 +144,34 @@ int lz4m_pcompress_large_batch(const uint8_t* d_src, const int64_t* d_src_off, c
                                int32_t* d_out_len, int64_t n, int32_t max_len, void* d_work, size_t work_bytes,
                                lz4m_stream_t stream);
 
+/*
+ * Batched lz4.block.compress(mode="high_compression", compression=level)
+ * (_block.c:112-119 -> LZ4_compress_HC_continue on a fresh stream): a
+ * hash-chain ("HC") parse on the device (lz4m_hc.hip).  Every result is a
+ * valid LZ4 block near the size of LZ4_compress_HC at the same level, NOT
+ * byte-identical to lz4hc.c (as LZ4M_PARSE_PARALLEL is to
+ * LZ4_compress_default): the parse is the serial algorithm of DESIGN.md
+ * section 9, which tests/hc_model/hc_model.c restates on the CPU byte for byte.
+ * `level` as in lz4hc.c: below 1 means 9; 1-2 search 2 chain candidates per
+ * position, 3 -> 4, 4 -> 8, ... 9 -> 256; levels 10-12 and above search as 9
+ * (the reference's optimal parser is not built).  Blocks of any length up to
+ * LZ4_MAX_INPUT_SIZE; offsets are limited to 65535 (LZ4_DISTANCE_MAX).
+ * d_out_len[i] = compressed size, or 0 when this parse's block does not fit
+ * in d_dst_cap[i] bytes (an exact fit is accepted; nothing is written past
+ * the capacity).  d_work: lz4m_compress_hc_workspace_size(n, max_len) bytes
+ * of device scratch, 2-byte aligned, not shared with a concurrently running
+ * call (the wavefronts' chain tables: 256 KiB per block of the batch, at most
+ * 320 MiB; max_len, the longest block, does not change it today).  Two
+ * launches (blocks up to 64 KiB, longer blocks), stream-ordered, no host
+ * synchronisation, no allocation.  LZ4M_EINVAL: n < 0, or a missing or short
+ * workspace.
+ */
+size_t lz4m_compress_hc_workspace_size(int64_t n, int32_t max_len);
+int lz4m_compress_hc_batch(const uint8_t* d_src, const int64_t* d_src_off, const int32_t* d_src_len,
+                           uint8_t* d_dst, const int64_t* d_dst_off, const int32_t* d_dst_cap,
+                           int32_t* d_out_len, int64_t n, int level, void* d_work, size_t work_bytes,
+                           lz4m_stream_t stream);
+
 /* Library identification (mirrors LZ4_versionNumber, lz4.c:728, of the
  * format version this codec is bit-compatible with: 10904). */
 int lz4m_version_number(void);

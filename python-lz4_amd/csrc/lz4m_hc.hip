@@ -1,0 +1,417 @@
+// lz4m_hc.hip -- hash-chain ("HC") LZ4 block compressor for MI355X (gfx950):
+// lz4.block.compress(mode="high_compression"), batched.
+//
+// A valid LZ4 block for every input, near the size of LZ4_compress_HC at the
+// same level (DESIGN.md section 9 has the measured ratios), but NOT
+// byte-identical to lz4hc.c -- the contract LZ4M_PARSE_PARALLEL has towards
+// LZ4_compress_default.  The parse is defined serially in DESIGN.md section 9
+// and restated on the CPU by tests/hc_model/hc_model.c; this kernel produces
+// that model's bytes:
+//   - 13-bit hash of 4 bytes, head[h] = newest position with hash h, chain[p]
+//     = distance from p to the previous position with p's hash (0: none
+//     within 65535 bytes);
+//   - search(q, low): up to `attempts` chain candidates below q, newest
+//     first, each measured forwards from q (to n - 5) and, if >= 4 bytes
+//     match, backwards (the match may start down to `low`); the longest wins,
+//     the nearest among equals;
+//   - parse: M = search(ip, anchor); then, while a search at M's last two
+//     bytes (q = end(M) - 2, low = start(M)) finds a longer match M2, M is cut
+//     at M2's start (kept if >= 4 bytes remain) and M2 takes its place.
+//
+// Mapping: one wavefront per block, a persistent grid striding over the
+// batch.  The head table is the workgroup's LDS, cleared per block; the chain
+// table is the wave's slice of the caller's workspace and is never read
+// before it is written within a block, so a block's bytes do not depend on
+// the wave that parsed it.
+//   - Insertion runs ahead of the parse, 64 consecutive positions per step;
+//     lanes that share a hash are linked by ballots over the hash bits (no
+//     atomics, no reliance on the order in which one instruction's lanes
+//     reach the LDS).  Position q's own chain entry is then what head[h(q)]
+//     held before q went in, so a search starts from chain[q] and never sees
+//     a position >= q, however far insertion has run ahead.
+//   - Where no match is pending, 64 positions walk their own chains at once,
+//     comparing four bytes per candidate, and the parse jumps to the first
+//     position at which a search will find a match.
+//   - A search gathers up to 64 chain candidates (one dependent 2-byte load
+//     each, the address uniform), then every lane measures its own candidate
+//     and a wave maximum picks the winner: the memory round trips of the
+//     comparisons are paid once per 64 candidates.
+// The kernel is bound by the latency of these dependent loads, so what counts
+// is the number of resident waves, which the head table decides (HcCfg).
+#include "lz4m_common.h"
+
+#include "../../include/lz4m.h"
+
+namespace lz4m {
+namespace {
+
+constexpr int kHcHashBits = 13;
+constexpr int kHcHeads = 1 << kHcHashBits;
+constexpr int32_t kHcMaxDist = 65535;    // LZ4_DISTANCE_MAX
+constexpr int32_t kHcSmallMax = 65536;   // longest block of the u16-head kernel
+constexpr int32_t kHcMaxInput = 0x7E000000;
+
+// Two kernels share the parse.  Blocks up to 64 KiB: u16 heads (position + 1
+// <= 65525; 16 KiB of LDS, 10 workgroups per CU of 160 KiB) and a chain
+// indexed by the position.  Longer blocks: u32 heads (32 KiB, 5 per CU) and a
+// chain of 2 x 65536 entries indexed by the position mod 131072: positions
+// are inserted up to 127 ahead of a search, and a window of exactly 65536
+// entries would overwrite that search's oldest candidates.
+template <bool BIG>
+struct HcCfg {
+    typedef uint16_t head_t;
+    static constexpr int kWaves = 2560;
+    static constexpr uint32_t kChain = 65536;
+};
+template <>
+struct HcCfg<true> {
+    typedef uint32_t head_t;
+    static constexpr int kWaves = 1280;
+    static constexpr uint32_t kChain = 131072;
+};
+// both kernels' slices fill the same workspace (they run one after the other)
+constexpr size_t kHcWorkMax = (size_t)HcCfg<false>::kWaves * HcCfg<false>::kChain * sizeof(uint16_t);
+static_assert(kHcWorkMax == (size_t)HcCfg<true>::kWaves * HcCfg<true>::kChain * sizeof(uint16_t), "shared workspace");
+
+__device__ __forceinline__ uint32_t hc_uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+__device__ __forceinline__ int32_t hc_rdl(int32_t v, int l) { return __builtin_amdgcn_readlane(v, l); }
+__device__ __forceinline__ uint32_t hc_hash(uint32_t v) { return (v * 2654435761u) >> (32 - kHcHashBits); }
+
+// accesses of one lane that another lane of the wave made or will make:
+// relaxed atomics at wavefront scope (plain loads and stores in the ISA),
+// ordered by hc_fence
+template <typename T>
+__device__ __forceinline__ uint32_t hc_ld(const T* p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+}
+template <typename T>
+__device__ __forceinline__ void hc_st(T* p, uint32_t v) {
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+}
+__device__ __forceinline__ void hc_fence() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); }
+
+// the wave's largest v (v >= 0), uniform: row_shr / row_bcast prefix maximum read at lane 63
+__device__ __forceinline__ int32_t hc_wave_max(int32_t v) {
+    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, false));   // row_shr:1
+    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, false));   // row_shr:2
+    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, false));   // row_shr:4
+    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, false));   // row_shr:8
+    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, false));   // row_bcast:15 -> rows 1, 3
+    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, false));   // row_bcast:31 -> rows 2, 3
+    return hc_rdl(v, 63);
+}
+
+// The parse state of one block.  Everything is uniform across the wave.
+template <bool BIG>
+struct HcBlock {
+    typedef __attribute__((address_space(3))) typename HcCfg<BIG>::head_t head_t;
+    static constexpr uint32_t kMask = HcCfg<BIG>::kChain - 1u;
+
+    head_t* head;
+    uint16_t* chain;
+    const uint8_t* src;
+    int32_t n;
+    int32_t ilimit;     // positions below it can be inserted (n - 11: each has 4 bytes and may start a match)
+    int32_t inserted;   // positions below it are in the tables
+    int32_t attempts;
+    uint32_t lane;
+
+    // Insert 64 positions per step until position q is in.  Lane l's position
+    // chains to the nearest earlier lane of the step with the same hash, else
+    // to the table's entry; the last lane of each hash writes the table.
+    __device__ __forceinline__ void insert_through(int32_t q) {
+        while (inserted <= q) {
+            const int32_t base = inserted;
+            const int32_t end = base + kWave < ilimit ? base + kWave : ilimit;
+            const int32_t p = base + (int32_t)lane;
+            const bool act = p < end;
+            uint32_t h = 0;
+            if (act) h = hc_hash(ld32(src + p));
+            uint64_t same = __ballot(act);
+#pragma unroll
+            for (int b = 0; b < kHcHashBits; ++b) {
+                const bool bit = (h >> b) & 1u;
+                const uint64_t B = __ballot(bit);
+                same &= bit ? B : ~B;
+            }
+            if (act) {
+                const uint64_t below = same & ((1ull << lane) - 1ull);
+                const uint64_t above = same & ~((2ull << lane) - 1ull);
+                const uint32_t prev = below ? (uint32_t)base + (63u - (uint32_t)__builtin_clzll(below)) + 1u
+                                            : hc_ld(head + h);
+                const uint32_t d = prev ? (uint32_t)p + 1u - prev : 0u;
+                hc_st(chain + ((uint32_t)p & kMask), d > (uint32_t)kHcMaxDist ? 0u : d);
+                if (above == 0) hc_st(head + h, (uint32_t)p + 1u);
+            }
+            hc_fence();
+            inserted = end;
+        }
+    }
+
+    // The first position >= ip (and <= mflimit) at which search() finds a
+    // match, or mflimit + 1.  search(p, .) finds one exactly when one of p's
+    // first `attempts` chain candidates has p's four bytes (a search position
+    // has >= 7 bytes to match), so 64 positions walk their own chains at
+    // once, a step per candidate, until the lowest position with such a
+    // candidate has no undecided position below it.
+    __device__ __forceinline__ int32_t next_candidate(int32_t ip, int32_t mflimit) {
+        while (ip <= mflimit) {
+            const int32_t last = ip + kWave - 1 < mflimit ? ip + kWave - 1 : mflimit;
+            insert_through(last);
+            const int32_t p = ip + (int32_t)lane;
+            uint32_t cur = 0, want = 0;   // cur: candidate position + 1, 0 = none
+            if (p <= last) {
+                const uint32_t d = hc_ld(chain + ((uint32_t)p & kMask));
+                cur = d ? (uint32_t)p + 1u - d : 0u;
+                want = ld32(src + p);
+            }
+            // (a candidate lies below p and within the window by construction; checked all the same)
+            bool open = cur != 0 && cur <= (uint32_t)p, hit = false;
+            for (int32_t left = attempts; left > 0; --left) {
+                if (open) {
+                    const uint32_t c = cur - 1u;
+                    const uint32_t got = ld32(src + c);
+                    const uint32_t d = hc_ld(chain + (c & kMask));
+                    if (got == want) {
+                        hit = true;
+                        open = false;
+                    } else {
+                        cur = d ? cur - d : 0u;
+                        open = cur != 0 && cur <= (uint32_t)p && p - (int32_t)(cur - 1u) <= kHcMaxDist;
+                    }
+                }
+                const uint64_t hits = __ballot(hit), opens = __ballot(open);
+                const int fh = hits ? __builtin_ctzll(hits) : kWave, fo = opens ? __builtin_ctzll(opens) : kWave;
+                if (fh < fo) return ip + fh;   // every position below it is decided: no match there
+                if (opens == 0) break;
+            }
+            // a position still open after `attempts` candidates has none; so has every position below a late hit
+            const uint64_t hits = __ballot(hit);
+            if (hits) return ip + (int32_t)__builtin_ctzll(hits);
+            ip = last + 1;
+        }
+        return ip;
+    }
+};
+
+// equal leading bytes of a[..] and b[..], at most lim; reads stay below a + lim and b + lim
+__device__ __forceinline__ int32_t hc_count(const uint8_t* a, const uint8_t* b, int32_t lim) {
+    int32_t k = 0;
+    while (k + 8 <= lim) {
+        const uint64_t x = ld64(a + k) ^ ld64(b + k);
+        if (x) return k + (int32_t)(__builtin_ctzll(x) >> 3);
+        k += 8;
+    }
+    while (k < lim && a[k] == b[k]) ++k;
+    return k;
+}
+
+// equal bytes going backwards from a[-1] and b[-1], at most lim; reads stay at or above a - lim and b - lim
+__device__ __forceinline__ int32_t hc_count_back(const uint8_t* a, const uint8_t* b, int32_t lim) {
+    int32_t k = 0;
+    while (k + 8 <= lim) {
+        const uint64_t x = ld64(a - k - 8) ^ ld64(b - k - 8);
+        if (x) return k + (int32_t)(__builtin_clzll(x) >> 3);
+        k += 8;
+    }
+    while (k < lim && a[-k - 1] == b[-k - 1]) ++k;
+    return k;
+}
+
+struct HcMatch {
+    int32_t len, start, pos;   // len 0: none
+};
+
+// search(q, low); q is inserted.  All values uniform.
+template <bool BIG>
+__device__ __forceinline__ HcMatch hc_search(HcBlock<BIG>& s, int32_t q, int32_t low) {
+    constexpr uint32_t kMask = HcBlock<BIG>::kMask;
+    const uint8_t* src = s.src;
+    const int32_t lim = s.n - 5 - q;
+    HcMatch m{0, 0, 0};
+    // q's own entry: the newest position below q with its hash (position + 1, 0 = none)
+    uint32_t cur = hc_uni(hc_ld(s.chain + ((uint32_t)q & kMask)));
+    cur = cur ? (uint32_t)q + 1u - cur : 0u;
+    int32_t left = s.attempts;
+    while (left > 0 && cur != 0 && q - (int32_t)(cur - 1u) <= kHcMaxDist) {
+        // one lane's worth of the chain per candidate, newest in lane 0
+        const int32_t take = left < kWave ? left : kWave;
+        int32_t cnt = 0, mine = -1;
+        do {
+            if ((int32_t)s.lane == cnt) mine = (int32_t)(cur - 1u);
+            ++cnt;
+            const uint32_t d = hc_uni(hc_ld(s.chain + ((cur - 1u) & kMask)));
+            cur = d ? cur - d : 0u;
+        } while (cnt < take && cur != 0 && q - (int32_t)(cur - 1u) <= kHcMaxDist);
+        left -= cnt;
+        int32_t tot = 0, back = 0;
+        if (mine >= 0 && mine < q) {
+            const int32_t fwd = hc_count(src + mine, src + q, lim);
+            if (fwd >= 4) {
+                back = hc_count_back(src + q, src + mine, q - low < mine ? q - low : mine);
+                tot = fwd + back;
+            }
+        }
+        const int32_t best = hc_wave_max(tot);
+        if (best > m.len) {
+            const int l = __builtin_ctzll(__ballot(tot == best));   // the nearest of the longest
+            const int32_t bk = hc_rdl(back, l);
+            m.len = best;
+            m.start = q - bk;
+            m.pos = hc_rdl(mine, l) - bk;
+            if (best == lim + q - low) break;   // nothing longer exists
+        }
+    }
+    return m;
+}
+
+__device__ __forceinline__ int32_t hc_ext_bytes(int32_t v) { return v >= 15 ? 1 + (v - 15) / 255 : 0; }
+
+// the e = hc_ext_bytes(v) length bytes of v at o
+__device__ __forceinline__ void hc_put_ext(uint8_t* o, int32_t v, int32_t e, uint32_t lane) {
+    if (e == 0) return;
+    for (int32_t k = (int32_t)lane; k < e - 1; k += kWave) o[k] = 255;
+    if (lane == 0) o[e - 1] = (uint8_t)(v - 15 - 255 * (e - 1));
+}
+
+// One sequence at dst + op: ll literals from src + anchor, then (ml > 0) a
+// match of ml bytes at distance off; ml == 0 is the block's last sequence.
+// False (nothing written) if it does not fit in cap.
+__device__ __forceinline__ bool hc_emit(uint8_t* dst, int32_t& op, int32_t cap, const uint8_t* src, int32_t anchor,
+                                        int32_t ll, int32_t off, int32_t ml, uint32_t lane) {
+    const int32_t le = hc_ext_bytes(ll), me = ml ? hc_ext_bytes(ml - 4) : 0;
+    const int64_t need = 1 + (int64_t)le + ll + (ml ? 2 + me : 0);
+    if ((int64_t)op + need > (int64_t)cap) return false;
+    uint8_t* o = dst + op;
+    if (lane == 0) {
+        const int32_t mt = ml ? (ml - 4 < 15 ? ml - 4 : 15) : 0;
+        o[0] = (uint8_t)(((ll < 15 ? ll : 15) << 4) | mt);
+    }
+    hc_put_ext(o + 1, ll, le, lane);
+    uint8_t* lit = o + 1 + le;
+    for (int32_t k = (int32_t)lane; k < ll; k += kWave) lit[k] = src[anchor + k];
+    if (ml) {
+        uint8_t* mo = lit + ll;
+        if (lane == 0) {
+            mo[0] = (uint8_t)(off & 0xFF);
+            mo[1] = (uint8_t)(off >> 8);
+        }
+        hc_put_ext(mo + 2, ml - 4, me, lane);
+    }
+    op += (int32_t)need;
+    return true;
+}
+
+// BIG = false: the blocks of up to kHcSmallMax bytes; BIG = true: the longer ones.
+template <bool BIG>
+__global__ __launch_bounds__(64) void hc_compress_kernel(const uint8_t* __restrict__ src_base,
+                                                         const int64_t* __restrict__ src_off,
+                                                         const int32_t* __restrict__ src_len,
+                                                         uint8_t* __restrict__ dst_base,
+                                                         const int64_t* __restrict__ dst_off,
+                                                         const int32_t* __restrict__ dst_cap,
+                                                         int32_t* __restrict__ out_len, int64_t nblocks,
+                                                         int32_t attempts, uint16_t* __restrict__ work) {
+    typedef typename HcCfg<BIG>::head_t head_mem_t;
+    __shared__ __attribute__((aligned(16))) head_mem_t head_mem[kHcHeads];
+    HcBlock<BIG> s;
+    s.head = (typename HcBlock<BIG>::head_t*)head_mem;
+    s.chain = work + (size_t)blockIdx.x * HcCfg<BIG>::kChain;
+    s.attempts = attempts;
+    s.lane = threadIdx.x;
+    const uint32_t lane = s.lane;
+    for (int64_t b = blockIdx.x; b < nblocks; b += gridDim.x) {
+        const int32_t n = src_len[b];
+        if ((n > kHcSmallMax) != BIG) continue;   // the other kernel's block
+        const int32_t cap = dst_cap[b];
+        const uint8_t* src = src_base + src_off[b];
+        uint8_t* dst = dst_base + dst_off[b];
+        if (n < 0 || n > kHcMaxInput || cap < 0) {
+            if (lane == 0) out_len[b] = 0;
+            continue;
+        }
+        int32_t op = 0, anchor = 0;
+        bool fits = true;
+        if (n >= 13) {
+            for (int32_t i = (int32_t)lane; i < kHcHeads; i += kWave) hc_st(s.head + i, 0u);
+            hc_fence();
+            const int32_t mflimit = n - 12;
+            s.src = src;
+            s.n = n;
+            s.ilimit = mflimit + 1;
+            s.inserted = 0;
+            int32_t ip = 0;
+            while ((ip = s.next_candidate(ip, mflimit)) <= mflimit) {
+                HcMatch m = hc_search(s, ip, anchor);
+                if (m.len == 0) {
+                    ++ip;
+                    continue;
+                }
+                for (;;) {   // probe the end of the match for a longer one that overlaps it
+                    const int32_t q = m.start + m.len - 2;
+                    if (q > mflimit) break;
+                    s.insert_through(q);
+                    const HcMatch m2 = hc_search(s, q, m.start);
+                    if (m2.len <= m.len) break;
+                    if (m2.start - m.start >= 4) {   // keep the head of the first match
+                        fits = hc_emit(dst, op, cap, src, anchor, m.start - anchor, m.start - m.pos,
+                                       m2.start - m.start, lane);
+                        if (!fits) break;
+                        anchor = m2.start;
+                    }
+                    m = m2;
+                }
+                if (fits) fits = hc_emit(dst, op, cap, src, anchor, m.start - anchor, m.start - m.pos, m.len, lane);
+                if (!fits) break;
+                ip = m.start + m.len;
+                anchor = ip;
+            }
+        }
+        if (fits) fits = hc_emit(dst, op, cap, src, anchor, n - anchor, 0, 0, lane);
+        if (lane == 0) out_len[b] = fits ? op : 0;
+    }
+}
+
+// lz4hc.c level table: levels below 1 mean 9; 1-2 -> 2 attempts, 3 -> 4, ...
+// 9 -> 256; the optimal parser of levels 10-12 is not built (they search as 9)
+int32_t hc_attempts(int level) {
+    if (level < 1) level = 9;
+    if (level > 9) level = 9;
+    return level < 3 ? 2 : 1 << (level - 1);
+}
+
+}  // namespace
+}  // namespace lz4m
+
+extern "C" size_t lz4m_compress_hc_workspace_size(int64_t n, int32_t max_len) {
+    using namespace lz4m;
+    if (n <= 0 || max_len < 0) return 0;
+    // the longer blocks' kernel has half the waves with slices twice as large
+    const int64_t waves = n < HcCfg<false>::kWaves ? n : HcCfg<false>::kWaves;
+    const size_t bytes = (size_t)waves * HcCfg<true>::kChain * sizeof(uint16_t);
+    return bytes < kHcWorkMax ? bytes : kHcWorkMax;
+}
+
+extern "C" int lz4m_compress_hc_batch(const uint8_t* d_src, const int64_t* d_src_off, const int32_t* d_src_len,
+                                      uint8_t* d_dst, const int64_t* d_dst_off, const int32_t* d_dst_cap,
+                                      int32_t* d_out_len, int64_t n, int level, void* d_work, size_t work_bytes,
+                                      lz4m_stream_t stream) {
+    using namespace lz4m;
+    if (n < 0) return LZ4M_EINVAL;
+    if (n == 0) return 0;
+    if (d_work == nullptr || ((uintptr_t)d_work & 1u) || work_bytes < lz4m_compress_hc_workspace_size(n, 0))
+        return LZ4M_EINVAL;
+    const int32_t attempts = hc_attempts(level);
+    hipStream_t st = (hipStream_t)stream;
+    // both kernels walk the whole batch and take their own blocks; a wave
+    // whose share holds none of them ends after reading its blocks' lengths
+    const uint32_t small_grid = (uint32_t)(n < HcCfg<false>::kWaves ? n : HcCfg<false>::kWaves);
+    hipLaunchKernelGGL(hc_compress_kernel<false>, dim3(small_grid), dim3(64), 0, st, d_src, d_src_off, d_src_len,
+                       d_dst, d_dst_off, d_dst_cap, d_out_len, n, attempts, (uint16_t*)d_work);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    const uint32_t big_grid = (uint32_t)(n < HcCfg<true>::kWaves ? n : HcCfg<true>::kWaves);
+    hipLaunchKernelGGL(hc_compress_kernel<true>, dim3(big_grid), dim3(64), 0, st, d_src, d_src_off, d_src_len,
+                       d_dst, d_dst_off, d_dst_cap, d_out_len, n, attempts, (uint16_t*)d_work);
+    return (int)hipGetLastError();
+}

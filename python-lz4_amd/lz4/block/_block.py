@@ -60,7 +60,8 @@ def _buffer(obj, name: str = "source") -> memoryview:
     return mv.cast("B") if mv.format != "B" or mv.ndim != 1 else mv
 
 
-def _mode_accel(mode, acceleration: int) -> int:
+def _mode_accel(mode, acceleration: int) -> int | None:
+    """The acceleration of the non-HC modes; None for 'high_compression'."""
     if not isinstance(mode, str):
         raise TypeError(f"compress() argument 'mode' must be str, not {type(mode).__name__}")
     if mode == "default":
@@ -68,10 +69,18 @@ def _mode_accel(mode, acceleration: int) -> int:
     if mode == "fast":
         return acceleration
     if mode == "high_compression":
-        raise NotImplementedError(
-            "mode='high_compression' (LZ4 HC) is outside the MI355X codec's scope; "
-            "use mode='default' or mode='fast'")
+        return None
     raise ValueError(f"Invalid mode argument: {mode}. Must be one of: standard, fast, high_compression")
+
+
+def _hc_mode(mode) -> bool:
+    """``mode`` of the batched calls: "default" (the exact compressors, chosen
+    by their own ``table`` / ``accel`` arguments) or "high_compression"."""
+    if mode == "default":
+        return False
+    if mode == "high_compression":
+        return True
+    raise ValueError(f"Invalid mode argument: {mode}. Must be one of: default, high_compression")
 
 
 _probe = b"lz4m"
@@ -112,10 +121,18 @@ def compress(source, mode="default", store_size=True, acceleration=1, compressio
     hash5), which ``TABLE_U32_HASH5`` reproduces.  With ``dict`` (any
     length, even empty) the stream is first loaded with ``LZ4_loadDict``
     (``_block.c:101-104``, ``lz4.c:1541-1581``) -- lz4m_compress_dict_batch.
+
+    ``mode='high_compression'`` (``_block.c:112-119``) runs the device's
+    hash-chain compressor at level ``compression`` (lz4m_compress_hc_batch):
+    a valid block near the size of ``LZ4_compress_HC`` at that level, NOT
+    byte-identical to it.  Levels below 1 mean 9; levels 10-12 and above
+    search as level 9 (the reference's optimal parser is not built).  HC with
+    ``dict=`` (``LZ4_loadDictHC``) is not built and raises
+    ``NotImplementedError``.
     """
     src = _buffer(source)
     acceleration = _c_int(acceleration, "acceleration")
-    _c_int(compression, "compression")
+    compression = _c_int(compression, "compression")
     if src.nbytes > INT_MAX:
         raise OverflowError("Input too large for LZ4 API")
     d = None
@@ -124,6 +141,16 @@ def compress(source, mode="default", store_size=True, acceleration=1, compressio
         if d.nbytes > INT_MAX:
             raise OverflowError("Dictionary too large for LZ4 API")
     accel = _mode_accel(mode, acceleration)
+    if accel is None:
+        if d is not None:
+            raise NotImplementedError(
+                "mode='high_compression' with dict= (LZ4_loadDictHC) is not built on the MI355X codec; "
+                "compress without a dictionary, or use mode='default' or mode='fast' with dict=")
+        out = compress_many([src], store_size=bool(store_size), as_bytearray=bool(return_bytearray),
+                            mode="high_compression", compression=compression)[0]
+        if out is None:
+            raise LZ4BlockError("Compression failed")
+        return out
     if d is None:   # one call: lz4m_compress_block_api (one launch on mapped pinned staging)
         N.require_device()
         n = src.nbytes
@@ -321,14 +348,23 @@ def _stage_out(lay: _Layout, h: torch.Tensor, d: torch.Tensor, n: int):
 
 
 def compress_many(blocks, accel: int = 1, store_size: bool = True, as_bytearray: bool = False,
-                  table: int = N.TABLE_U32_HASH5, dict=None, dict_prefix: bool = False):
+                  table: int = N.TABLE_U32_HASH5, dict=None, dict_prefix: bool = False,
+                  mode: str = "default", compression: int = 9):
     """Compress a sequence of host buffers as independent blocks in one
     launch.  Returns a list of bytes (None for a block that failed, i.e.
     input larger than LZ4_MAX_INPUT_SIZE).  ``dict`` (a buffer, possibly
     empty): every block is compressed as lz4.block.compress(dict=dict) does;
     the dictionary's last 64 KiB are staged in front of each block.
     ``dict_prefix``: compress as the reference does when the dictionary's
-    memory ends where each source begins (prefix mode, lz4.c:1671)."""
+    memory ends where each source begins (prefix mode, lz4.c:1671).
+    ``mode="high_compression"``: the hash-chain compressor at level
+    ``compression`` (valid blocks near LZ4_compress_HC's size, not
+    byte-identical; ``accel`` and ``table`` are ignored, ``dict`` is not
+    built)."""
+    hc = _hc_mode(mode)
+    compression = _c_int(compression, "compression")
+    if hc and dict is not None:
+        raise NotImplementedError("mode='high_compression' with dict= (LZ4_loadDictHC) is not built")
     views = [_buffer(b) for b in blocks]
     dev = N.device()
     n = len(views)
@@ -349,7 +385,10 @@ def compress_many(blocks, accel: int = 1, store_size: bool = True, as_bytearray:
         payload = [x for v in views for x in (tail, v)]
     lay, h, d = _stage_in(dev, payload, offs, lens, d_off, caps)
     d_src, src_off, src_len, d_dst, dst_off, dst_cap, out_len = _dev_views(lay, d, n)
-    if dict is None:
+    if hc:
+        N.launch_compress_hc(d_src, src_off, src_len, d_dst, dst_off, dst_cap, out_len, n, compression,
+                             max_len=max(lens))
+    elif dict is None:
         N.launch_compress(d_src, src_off, src_len, d_dst, dst_off, dst_cap, out_len, n, table, accel)
     else:
         dict_len = torch.full((n,), dv.nbytes, dtype=torch.int32, device=dev)
@@ -458,7 +497,8 @@ def decompress_many(blocks, uncompressed_size=-1, dict=None, as_bytearray: bool 
 # ------------------------------------------------- device-resident batches
 def compress_batch(src: torch.Tensor, src_off: torch.Tensor, src_len: torch.Tensor, *,
                    table: str | int = "block", acceleration: int = 1, dst: torch.Tensor | None = None,
-                   dst_off: torch.Tensor | None = None, dst_cap: torch.Tensor | None = None, stream=None):
+                   dst_off: torch.Tensor | None = None, dst_cap: torch.Tensor | None = None, stream=None,
+                   mode: str = "default", compression: int = 9):
     """Compress n device-resident blocks in one stream-ordered launch.
 
     ``src`` uint8 (HBM), ``src_off`` int64[n], ``src_len`` int32[n].
@@ -467,7 +507,17 @@ def compress_batch(src: torch.Tensor, src_off: torch.Tensor, src_len: torch.Tens
     TABLE_* constant.  Output slots default to LZ4_compressBound(len) each.
     Returns (dst, dst_off, out_len) with out_len int32[n] (0 = did not fit).
     No host synchronisation.
+
+    ``mode="high_compression"``: the hash-chain (HC) compressor at level
+    ``compression`` instead (lz4m_compress_hc_batch; ``table`` and
+    ``acceleration`` are ignored): valid blocks near the size of
+    LZ4_compress_HC at that level, NOT byte-identical to it.  Levels below 1
+    mean 9, 3..9 search 4..256 chain candidates per position, levels 10-12
+    and above search as 9 (the reference's optimal parser is not built).  A
+    block that does not fit its slot reports 0; an exact fit is accepted.
     """
+    hc = _hc_mode(mode)
+    compression = _c_int(compression, "compression")
     tab = {"block": N.TABLE_U32_HASH5, "default": N.TABLE_AUTO, "u16": N.TABLE_U16_HASH4}.get(table, table)
     n = src_off.numel()
     dev = src.device
@@ -479,7 +529,12 @@ def compress_batch(src: torch.Tensor, src_off: torch.Tensor, src_len: torch.Tens
         total = int((dst_off[-1] + dst_cap[-1]).item()) if n else 1
         dst = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
     out_len = torch.empty(n, dtype=torch.int32, device=dev)
-    N.launch_compress(src, src_off, src_len, dst, dst_off, dst_cap, out_len, n, int(tab), int(acceleration), stream)
+    if hc:
+        if n:
+            N.launch_compress_hc(src, src_off, src_len, dst, dst_off, dst_cap, out_len, n, compression, stream)
+    else:
+        N.launch_compress(src, src_off, src_len, dst, dst_off, dst_cap, out_len, n, int(tab), int(acceleration),
+                          stream)
     return dst, dst_off, out_len
 
 
