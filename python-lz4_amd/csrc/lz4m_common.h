@@ -37,11 +37,6 @@ __device__ __forceinline__ uint64_t ld64(const uint8_t* p) {
     __builtin_memcpy(&v, p, 8);
     return v;
 }
-__device__ __forceinline__ uint32_t ld16le(const uint8_t* p) {
-    uint16_t v;
-    __builtin_memcpy(&v, p, 2);
-    return v;
-}
 
 // 16 bytes at p, with bytes at or beyond `avail` read as zero (never
 // touches memory past p + avail).
@@ -203,6 +198,7 @@ __device__ __forceinline__ u32x4 period_perm(u32x4 w, lds_cu32* sel) {
     return r;
 }
 
+// -------------------------------------------------------- lane broadcast
 __device__ __forceinline__ uint32_t lane_id() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 
 __device__ __forceinline__ int64_t readlane64(int64_t v, int lane) {
@@ -217,6 +213,136 @@ __device__ __forceinline__ T* readlane_ptr(T* p, int lane) {
     typedef __attribute__((address_space(1))) T gT;
     gT* g = (gT*)(uintptr_t)readlane64(reinterpret_cast<int64_t>(p), lane);
     return (T*)g;
+}
+// lane l's v / the first active lane's v, as a uniform value
+__device__ __forceinline__ int32_t rdl(int32_t v, int l) { return __builtin_amdgcn_readlane(v, l); }
+__device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+
+// ------------------------------------------------------------- DPP scans
+// Inclusive prefix scans, VALU only.  A row = 16 consecutive lanes: row_shr
+// 1/2/4/8 stays inside a row; row_bcast:15 / row_bcast:31 then carry the row
+// totals across the wave.
+__device__ __forceinline__ int32_t row_incl_sum(int32_t v) {
+    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, false);   // row_shr:1
+    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, false);   // row_shr:2
+    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, false);   // row_shr:4
+    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, false);   // row_shr:8
+    return v;
+}
+__device__ __forceinline__ int32_t wave_incl_sum(int32_t v) {
+    v = row_incl_sum(v);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, false);   // row_bcast:15 -> rows 1, 3
+    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, false);   // row_bcast:31 -> rows 2, 3
+    return v;
+}
+// prefix maximum (v >= 0: the identity is 0), the same steps
+__device__ __forceinline__ int32_t row_incl_max(int32_t v) {
+    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, false));
+    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, false));
+    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, false));
+    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, false));
+    return v;
+}
+__device__ __forceinline__ int32_t wave_incl_max(int32_t v) {
+    v = row_incl_max(v);
+    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, false));
+    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, false));
+    return v;
+}
+// the wave's largest v (v >= 0), uniform
+__device__ __forceinline__ int32_t wave_max(int32_t v) { return rdl(wave_incl_max(v), 63); }
+
+// ------------------------------------------------------ LZ4 block format
+// hash of 4 bytes into BITS bits (LZ4_hash4, lz4.c:756-762)
+template <int BITS>
+__device__ __forceinline__ uint32_t hash4(uint32_t v) { return (v * 2654435761u) >> (32 - BITS); }
+
+// y / 255 for y >= 0.  Blocks <= 64 KiB (!BIG): (z + z/256) / 256 with z =
+// y + 1, exact for y < 65 790 (checked exhaustively), two shifts and two adds
+// where the division is a quarter-rate v_mul_hi_u32
+template <bool BIG>
+__device__ __forceinline__ int32_t div255(int32_t y) {
+    if (BIG) return y / 255;
+    const int32_t z = y + 1;
+    return (z + (z >> 8)) >> 8;
+}
+// length bytes after the token for a length field x (0 below 15)
+template <bool BIG>
+__device__ __forceinline__ int32_t ext_len(int32_t x) { return x >= 15 ? 1 + div255<BIG>(x - 15) : 0; }
+
+// ------------------------------------------------------------ exact puts
+// Store exactly k (0..16) bytes of v at global address p (any alignment).
+__device__ __forceinline__ void put_exact(uint8_t* p, u32x4 v, uint32_t k) {
+    if (k == 16) {
+        st16(p, v);
+        return;
+    }
+    uint32_t o = 0;
+    if (k & 8) {
+        const uint64_t x = ((uint64_t)v.y << 32) | v.x;
+        __builtin_memcpy(p, &x, 8);
+        o = 8;
+    }
+    if (k & 4) {
+        const uint32_t x = window_dword(v, o);
+        __builtin_memcpy(p + o, &x, 4);
+        o += 4;
+    }
+    if (k & 2) {
+        const uint16_t x = (uint16_t)window_dword(v, o);
+        __builtin_memcpy(p + o, &x, 2);
+        o += 2;
+    }
+    if (k & 1) p[o] = (uint8_t)window_dword(v, o);
+}
+// The same for any k: nothing for k <= 0, 16 bytes for k >= 16 (k = the
+// bytes left of a copy taken in 16-byte pieces).
+__device__ __forceinline__ void gbl_put(uint8_t* p, u32x4 v, int32_t k) {
+    if (k >= 16) {
+        st16(p, v);
+    } else if (k > 0) {
+        put_exact(p, v, (uint32_t)k);
+    }
+}
+
+// -------------------------------------------------------- wild wave copy
+// Non-overlapping copy of len bytes by the whole wave (uniform arguments).
+// Wild: the tail may be written as a whole 16-byte piece where d_room and
+// s_room (the bytes of the block's own buffers from d / s on) allow it, like
+// the reference's wild copies; it never writes past d + d_room or reads past
+// s + s_room.  Each lane requests kU 16-byte pieces before storing any: a long
+// literal (a stored-looking block's 64 KiB) waits on one memory round trip
+// per 4 KiB instead of per 1 KiB (kU = 1 where registers are short: the
+// dictionary kernel).
+// SL: s points into LDS (the lone-block decoder's staged input): LDS reads,
+// which wait on no store, where a flat read of LDS waits for every store the
+// wave has in flight (one L2 write round trip per 4 KiB of a long literal).
+template <int kU = 4, bool SL = false>
+__device__ __forceinline__ void wave_copy_wild(uint8_t* d, const uint8_t* s, int64_t len, int64_t d_room,
+                                               int64_t s_room, uint32_t lane) {
+    for (int64_t base = 0; base < len; base += 16 * kWave * kU) {
+        u32x4 v[kU];
+#pragma unroll
+        for (int u = 0; u < kU; ++u) {
+            const int64_t pos = base + 16 * kWave * u + 16 * (int64_t)lane;
+            const bool whole = pos < len && (len - pos >= 16 || s_room - pos >= 16);
+            if constexpr (SL)
+                v[u] = whole ? lds_ld16a((const lds_u8*)(s + pos)) : u32x4{0, 0, 0, 0};
+            else
+                v[u] = whole ? ld16(s + pos) : u32x4{0, 0, 0, 0};
+        }
+#pragma unroll
+        for (int u = 0; u < kU; ++u) {
+            const int64_t pos = base + 16 * kWave * u + 16 * (int64_t)lane;
+            if (pos < len) {
+                if (len - pos >= 16 || (d_room - pos >= 16 && s_room - pos >= 16)) {
+                    st16(d + pos, v[u]);
+                } else {
+                    for (int64_t k = pos; k < len; ++k) d[k] = s[k];
+                }
+            }
+        }
+    }
 }
 
 }  // namespace lz4m

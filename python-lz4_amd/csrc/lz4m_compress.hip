@@ -74,9 +74,9 @@ template <>
 struct Table<LZ4M_TABLE_U16_HASH4> {   // 8192 x u16 (lz4.c:756-762, 839-843)
     static constexpr int kEntries = 8192;
     __device__ static __forceinline__ uint32_t hash(const uint8_t* p) {
-        return (ld32(p) * 2654435761u) >> (32 - 13);
+        return hash4<13>(ld32(p));
     }
-    __device__ static __forceinline__ uint32_t hash_v(u32x4 v) { return (v.x * 2654435761u) >> (32 - 13); }
+    __device__ static __forceinline__ uint32_t hash_v(u32x4 v) { return hash4<13>(v.x); }
     __device__ static __forceinline__ uint32_t get(const uint16_t* t, uint32_t h) { return ((const lds_t16*)t)[h]; }
     __device__ static __forceinline__ void put(uint16_t* t, uint32_t h, uint32_t v) { ((lds_t16*)t)[h] = (uint16_t)v; }
     // volatile: kept in program order, never forwarded (the probe reads back
@@ -170,50 +170,6 @@ struct Table<kTableU17> {
 // back what it read (positions increase with the lane, so that lane is the one
 // whose read value is below lane f+1's position).  Replaces a read, a probe
 // write, a read back and a loop over the colliding groups.
-
-__device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ int64_t uni64(int64_t v) {
-    const uint32_t lo = uni((uint32_t)v), hi = uni((uint32_t)((uint64_t)v >> 32));
-    return (int64_t)(((uint64_t)hi << 32) | lo);
-}
-
-// Coalesced copy of len bytes (wave-cooperative); never writes past d+d_room
-// or reads past s+s_room.
-// The source and destination never overlap: each lane requests four 16-byte
-// pieces before storing any (one memory round trip per 4 KiB, not per 1 KiB).
-__device__ __forceinline__ void wave_copy(uint8_t* d, const uint8_t* s, int64_t len, int64_t d_room,
-                                          int64_t s_room, uint32_t lane) {
-    constexpr int kU = 4;
-    for (int64_t base = 0; base < len; base += 16 * kWave * kU) {
-        u32x4 v[kU];
-#pragma unroll
-        for (int u = 0; u < kU; ++u) {
-            const int64_t pos = base + 16 * kWave * u + 16 * (int64_t)lane;
-            const bool whole = pos < len && (len - pos >= 16 || s_room - pos >= 16);
-            v[u] = whole ? ld16(s + pos) : u32x4{0, 0, 0, 0};
-        }
-#pragma unroll
-        for (int u = 0; u < kU; ++u) {
-            const int64_t pos = base + 16 * kWave * u + 16 * (int64_t)lane;
-            if (pos < len) {
-                if (len - pos >= 16 || (d_room - pos >= 16 && s_room - pos >= 16)) {
-                    st16(d + pos, v[u]);
-                } else {
-                    for (int64_t k = pos; k < len; ++k) d[k] = s[k];
-                }
-            }
-        }
-    }
-}
-
-// Exactly k bytes (k >= 16: 16) of v at global address p
-__device__ __forceinline__ void gbl_put_c(uint8_t* p, u32x4 v, int32_t k) {
-    if (k >= 16) {
-        st16(p, v);
-        return;
-    }
-    for (int32_t j = 0; j < k; ++j) p[j] = (uint8_t)byte_of(v, j);
-}
 
 // kTnMerge: at acceleration 1 the test of the next position after a
 // match (lz4.c:1207-1258) may be lane 0 of the next search step instead of a
@@ -749,7 +705,7 @@ last_literals:
                 last_lit[1] = anchor;
             }
         } else {
-            wave_copy(dst + op, w + anchor, run, cap - op, iend - anchor, lane);
+            wave_copy_wild(dst + op, w + anchor, run, cap - op, iend - anchor, lane);
         }
         op += run;
     }

@@ -54,31 +54,6 @@ struct Lane {
     bool fast, live;
 };
 
-// Store exactly k (0..16) bytes of v at p (any alignment).
-__device__ __forceinline__ void put_exact(uint8_t* p, u32x4 v, uint32_t k) {
-    if (k == 16) {
-        st16(p, v);
-        return;
-    }
-    uint32_t o = 0;
-    if (k & 8) {
-        const uint64_t x = ((uint64_t)v.y << 32) | v.x;
-        __builtin_memcpy(p, &x, 8);
-        o = 8;
-    }
-    if (k & 4) {
-        const uint32_t x = window_dword(v, o);
-        __builtin_memcpy(p + o, &x, 4);
-        o += 4;
-    }
-    if (k & 2) {
-        const uint16_t x = (uint16_t)window_dword(v, o);
-        __builtin_memcpy(p + o, &x, 2);
-        o += 2;
-    }
-    if (k & 1) p[o] = (uint8_t)window_dword(v, o);
-}
-
 // ------------------------------------------------ input reads (general path)
 // The general state machine reads the compressed block byte by byte (length
 // bytes, offsets) and in 16-byte pieces (token window, literals).
@@ -106,7 +81,7 @@ __device__ __forceinline__ void lane_copy(uint8_t* d, const uint8_t* s, int64_t 
 }
 
 // Overlapping LZ77 copy d[j] = d[j - off] (zeros when off == 0, lz4.c:478-485,
-// 2300-2307), by the owning lane.
+// 2300-2307), by the owning lane alone; wild inside room, as wave_match.
 __device__ __forceinline__ void lane_match(uint8_t* d, int64_t off, int64_t len, int64_t room) {
     if (off >= 16) {
         for (int64_t i = 0; i < len; i += 16) {
@@ -141,40 +116,8 @@ __device__ __forceinline__ void lane_match(uint8_t* d, int64_t off, int64_t len,
 
 // ---------------------------------------------------------- wave copies
 // All 64 lanes execute the same copy (uniform arguments).
-// Literal bytes never overlap their destination, so each lane requests four
-// 16-byte pieces before storing any: a long literal (a stored-looking block's
-// 64 KiB) waits on one memory round trip per 4 KiB instead of per 1 KiB.
-// SL: s points into LDS (the lone-block decoder's staged input): LDS reads,
-// which wait on no store, where a flat read of LDS waits for every store the
-// wave has in flight (one L2 write round trip per 4 KiB of a long literal).
-template <int kU = 4, bool SL = false>   // kU: pieces per lane per round trip (1 where registers are short: the dictionary kernel)
-__device__ __forceinline__ void wave_literal(uint8_t* d, const uint8_t* s, int64_t len, int64_t d_room,
-                                             int64_t s_room, uint32_t lane) {
-    for (int64_t base = 0; base < len; base += 16 * kWave * kU) {
-        u32x4 v[kU];
-#pragma unroll
-        for (int u = 0; u < kU; ++u) {
-            const int64_t pos = base + 16 * kWave * u + 16 * (int64_t)lane;
-            const bool whole = pos < len && (len - pos >= 16 || s_room - pos >= 16);
-            if constexpr (SL)
-                v[u] = whole ? lds_ld16a((const lds_u8*)(s + pos)) : u32x4{0, 0, 0, 0};
-            else
-                v[u] = whole ? ld16(s + pos) : u32x4{0, 0, 0, 0};
-        }
-#pragma unroll
-        for (int u = 0; u < kU; ++u) {
-            const int64_t pos = base + 16 * kWave * u + 16 * (int64_t)lane;
-            if (pos < len) {
-                if (len - pos >= 16 || (d_room - pos >= 16 && s_room - pos >= 16)) {
-                    st16(d + pos, v[u]);
-                } else {
-                    for (int64_t k = pos; k < len; ++k) d[k] = s[k];
-                }
-            }
-        }
-    }
-}
-
+// Literals go through wave_copy_wild; wave_match is the overlapping copy, 64
+// lanes, wild inside room (coop_copy_match is exact, row_copy_match 16 lanes).
 __device__ __forceinline__ void wave_match(uint8_t* d, int64_t off, int64_t len, int64_t room, uint32_t lane) {
     if (off >= 16) {
         // rows of W bytes whose sources all lie before the row: W <= off
@@ -487,7 +430,7 @@ __global__ __launch_bounds__(256) void decompress_kernel(const uint8_t* __restri
             if (RESUME) {
                 L.ip = resume[i].ip;
                 L.op = resume[i].op;
-                if (L.ip < 0) {   // a whole-literal block, decoded by rows_parse_kernel: op = its size
+                if (resume[i].ip == kRowsWholeLiteral) {   // decoded by rows_parse_kernel: op = its size
                     L.result = L.op;
                     L.live = false;
                 }
@@ -511,7 +454,7 @@ __global__ __launch_bounds__(256) void decompress_kernel(const uint8_t* __restri
                 const uint8_t* s = readlane_ptr(L.src, l);
                 const int64_t iend = readlane64(L.iend, l);
                 const int64_t dp = readlane64(lc.dpos, l), sp = readlane64(lc.arg, l), ln = readlane64(lc.len, l);
-                wave_literal(d + dp, s + sp, ln, oend - dp, iend - sp, lane);
+                wave_copy_wild(d + dp, s + sp, ln, oend - dp, iend - sp, lane);
                 __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
             }
             const int mk = __builtin_amdgcn_readlane(mc.kind, l);
@@ -552,29 +495,11 @@ __global__ __launch_bounds__(256) void decompress_kernel(const uint8_t* __restri
 // the state the reference would have, so bytes and statuses are identical.
 constexpr int kCoopIn = 1024;
 
-__device__ __forceinline__ void coop_put(uint8_t* p, u32x4 v, int32_t k) {
-    if (k >= 16) {
-        st16(p, v);
-    } else if (k > 0) {
-        put_exact(p, v, (uint32_t)k);
-    }
-}
-
-__device__ __forceinline__ int32_t coop_incl_sum(int32_t v) {
-    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, false);   // row_shr:1
-    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, false);   // row_shr:2
-    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, false);   // row_shr:4
-    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, false);   // row_shr:8
-    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, false);   // row_bcast:15
-    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, false);   // row_bcast:31
-    return v;
-}
-
 // Exact-length whole-wave copies (no wild bytes: other sequences' output may
-// already sit right after them).
-template <bool SL = false>   // SL: s points into LDS (as wave_literal)
+// already sit right after them), 64 lanes, 32-bit positions.
+template <bool SL = false>   // SL: s points into LDS (as wave_copy_wild)
 __device__ __forceinline__ void coop_copy_literal(uint8_t* d, const uint8_t* s, int32_t len, uint32_t lane) {
-    constexpr int kU = 4;   // four pieces requested before any is stored (as wave_literal)
+    constexpr int kU = 4;   // four pieces requested before any is stored (as wave_copy_wild)
     for (int32_t base = 0; base < len; base += 16 * kWave * kU) {
         u32x4 v[kU];
 #pragma unroll
@@ -588,7 +513,7 @@ __device__ __forceinline__ void coop_copy_literal(uint8_t* d, const uint8_t* s, 
 #pragma unroll
         for (int u = 0; u < kU; ++u) {
             const int32_t pos = base + 16 * kWave * u + 16 * (int32_t)lane;
-            if (pos < len) coop_put(d + pos, v[u], len - pos);
+            if (pos < len) gbl_put(d + pos, v[u], len - pos);
         }
     }
 }
@@ -598,14 +523,14 @@ __device__ __forceinline__ void coop_copy_match(uint8_t* d, int32_t off, int32_t
         const int32_t w = (off < 16 * kWave ? off : 16 * kWave) & ~15;   // rows whose sources precede them
         for (int32_t base = 0; base < len; base += w) {
             const int32_t pos = base + 16 * (int32_t)lane;
-            if (pos < base + w && pos < len) coop_put(d + pos, ld16(d + pos - off), len - pos);
+            if (pos < base + w && pos < len) gbl_put(d + pos, ld16(d + pos - off), len - pos);
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
         }
         return;
     }
     const u32x4 pat = period_pattern(ld16(d - off), (uint32_t)off);
     const int32_t step = 16 - (16 % off);
-    for (int32_t pos = step * (int32_t)lane; pos < len; pos += step * kWave) coop_put(d + pos, pat, len - pos);
+    for (int32_t pos = step * (int32_t)lane; pos < len; pos += step * kWave) gbl_put(d + pos, pat, len - pos);
 }
 
 // The sequence starting at t (relative to the LDS input window), w = its
@@ -668,7 +593,7 @@ __device__ __forceinline__ CoopSeq coop_parse(const lds_u8* IN, int32_t t, u32x4
 // must already be in HBM and visible to the wave.
 // DICT: the dlen bytes before dict_end are the block's dictionary
 // (LZ4_decompress_safe_usingDict, as decompress_kernel<true>).  SL: s points
-// into LDS (long literals read as LDS, wave_literal).
+// into LDS (long literals read as LDS, wave_copy_wild).
 template <bool DICT = false, bool SL = false>
 __device__ __forceinline__ int32_t coop_finish(const uint8_t* s, uint8_t* d, int32_t iend, int32_t oend, int32_t ip,
                                                int32_t op, bool fast, uint32_t lane, int32_t dlen = 0,
@@ -697,7 +622,7 @@ __device__ __forceinline__ int32_t coop_finish(const uint8_t* s, uint8_t* d, int
         if (__builtin_amdgcn_readlane(lc.kind, 0) != kNone) {
             const int64_t ie = readlane64(L.iend, 0);
             const int64_t dp = readlane64(lc.dpos, 0), sp = readlane64(lc.arg, 0), ln = readlane64(lc.len, 0);
-            wave_literal<DICT ? 1 : 4, SL>(d + dp, s + sp, ln, oe - dp, ie - sp, lane);   // DICT: registers are short
+            wave_copy_wild<DICT ? 1 : 4, SL>(d + dp, s + sp, ln, oe - dp, ie - sp, lane);   // DICT: registers are short
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
         }
         if (__builtin_amdgcn_readlane(mc.kind, 0) != kNone) {
@@ -986,7 +911,7 @@ __device__ __forceinline__ void hist_decompress_body(const uint8_t* __restrict__
                 ml += 4;
                 if (off < 1 || off > opm || opm + ml >= oend - 64) break;
                 for (int32_t c = F + 16 * (int32_t)lane; c < op; c += 16 * kWave)
-                    coop_put(d + c, lds_ld16(OB + (c - base)), op - c);
+                    gbl_put(d + c, lds_ld16(OB + (c - base)), op - c);
                 __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
                 coop_copy_literal<SOLO>(d + op, s + q, lit, lane);
                 __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
@@ -1008,7 +933,7 @@ __device__ __forceinline__ void hist_decompress_body(const uint8_t* __restrict__
             const CoopSeq q = coop_parse(IN, tk, w);
             const int32_t lit = q.lit, off = q.off, ml = q.ml, adv = q.adv;
             const int32_t len = act ? lit + ml : 0;
-            const int32_t o = op + coop_incl_sum(len) - len;
+            const int32_t o = op + wave_incl_sum(len) - len;
             const int32_t sabs = ib + myseq;
             // the reference's fast-loop margins (lz4.c:2004-2110, as fast_seq / decode_step)
             const bool lit_ok = q.litx ? ib + q.litpos + lit <= iend - 32 && o + lit <= oend - 32
@@ -1091,7 +1016,7 @@ __device__ __forceinline__ void hist_decompress_body(const uint8_t* __restrict__
         // flush the rest exactly, then the exact state machine from (ip, op)
         if (SOLO) LZ4M_WTS(ts, 4);
         for (int32_t c = F + 16 * (int32_t)lane; c < op; c += 16 * kWave)
-            coop_put(d + c, lds_ld16(OB + (c - base)), op - c);
+            gbl_put(d + c, lds_ld16(OB + (c - base)), op - c);
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
         if (SOLO) LZ4M_WTS(ts, 5);
         const int32_t r = coop_finish<DICT, SOLO>(s, d, iend, oend, ip, op, fast, lane, dlen, d + ddelta);
@@ -1208,7 +1133,7 @@ __global__ __launch_bounds__(64) void decompress_chain_kernel(const uint8_t* __r
         const uint8_t* s = src + src_off[b];
         uint8_t* d = dst + running;
         if (raw_flag[b]) {
-            wave_literal(d, s, len, len, len, lane);
+            wave_copy_wild(d, s, len, len, len, lane);
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
             if (lane == 0) status[b] = (int32_t)len;
             running += len;
@@ -1245,7 +1170,7 @@ __global__ __launch_bounds__(64) void decompress_chain_kernel(const uint8_t* __r
                 const uint8_t* ss = readlane_ptr(L.src, 0);
                 const int64_t iend = readlane64(L.iend, 0);
                 const int64_t dp = readlane64(lc.dpos, 0), sp = readlane64(lc.arg, 0), ln = readlane64(lc.len, 0);
-                wave_literal(dd + dp, ss + sp, ln, oend - dp, iend - sp, lane);
+                wave_copy_wild(dd + dp, ss + sp, ln, oend - dp, iend - sp, lane);
                 __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
             }
             if (__builtin_amdgcn_readlane(mc.kind, 0) != kNone) {

@@ -73,10 +73,6 @@ struct HcCfg<true> {
 constexpr size_t kHcWorkMax = (size_t)HcCfg<false>::kWaves * HcCfg<false>::kChain * sizeof(uint16_t);
 static_assert(kHcWorkMax == (size_t)HcCfg<true>::kWaves * HcCfg<true>::kChain * sizeof(uint16_t), "shared workspace");
 
-__device__ __forceinline__ uint32_t hc_uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ int32_t hc_rdl(int32_t v, int l) { return __builtin_amdgcn_readlane(v, l); }
-__device__ __forceinline__ uint32_t hc_hash(uint32_t v) { return (v * 2654435761u) >> (32 - kHcHashBits); }
-
 // accesses of one lane that another lane of the wave made or will make:
 // relaxed atomics at wavefront scope (plain loads and stores in the ISA),
 // ordered by hc_fence
@@ -89,17 +85,6 @@ __device__ __forceinline__ void hc_st(T* p, uint32_t v) {
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
 }
 __device__ __forceinline__ void hc_fence() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); }
-
-// the wave's largest v (v >= 0), uniform: row_shr / row_bcast prefix maximum read at lane 63
-__device__ __forceinline__ int32_t hc_wave_max(int32_t v) {
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, false));   // row_shr:1
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, false));   // row_shr:2
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, false));   // row_shr:4
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, false));   // row_shr:8
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, false));   // row_bcast:15 -> rows 1, 3
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, false));   // row_bcast:31 -> rows 2, 3
-    return hc_rdl(v, 63);
-}
 
 // The parse state of one block.  Everything is uniform across the wave.
 template <bool BIG>
@@ -126,7 +111,7 @@ struct HcBlock {
             const int32_t p = base + (int32_t)lane;
             const bool act = p < end;
             uint32_t h = 0;
-            if (act) h = hc_hash(ld32(src + p));
+            if (act) h = hash4<kHcHashBits>(ld32(src + p));
             uint64_t same = __ballot(act);
 #pragma unroll
             for (int b = 0; b < kHcHashBits; ++b) {
@@ -230,7 +215,7 @@ __device__ __forceinline__ HcMatch hc_search(HcBlock<BIG>& s, int32_t q, int32_t
     const int32_t lim = s.n - 5 - q;
     HcMatch m{0, 0, 0};
     // q's own entry: the newest position below q with its hash (position + 1, 0 = none)
-    uint32_t cur = hc_uni(hc_ld(s.chain + ((uint32_t)q & kMask)));
+    uint32_t cur = uni(hc_ld(s.chain + ((uint32_t)q & kMask)));
     cur = cur ? (uint32_t)q + 1u - cur : 0u;
     int32_t left = s.attempts;
     while (left > 0 && cur != 0 && q - (int32_t)(cur - 1u) <= kHcMaxDist) {
@@ -240,7 +225,7 @@ __device__ __forceinline__ HcMatch hc_search(HcBlock<BIG>& s, int32_t q, int32_t
         do {
             if ((int32_t)s.lane == cnt) mine = (int32_t)(cur - 1u);
             ++cnt;
-            const uint32_t d = hc_uni(hc_ld(s.chain + ((cur - 1u) & kMask)));
+            const uint32_t d = uni(hc_ld(s.chain + ((cur - 1u) & kMask)));
             cur = d ? cur - d : 0u;
         } while (cnt < take && cur != 0 && q - (int32_t)(cur - 1u) <= kHcMaxDist);
         left -= cnt;
@@ -252,22 +237,20 @@ __device__ __forceinline__ HcMatch hc_search(HcBlock<BIG>& s, int32_t q, int32_t
                 tot = fwd + back;
             }
         }
-        const int32_t best = hc_wave_max(tot);
+        const int32_t best = wave_max(tot);
         if (best > m.len) {
             const int l = __builtin_ctzll(__ballot(tot == best));   // the nearest of the longest
-            const int32_t bk = hc_rdl(back, l);
+            const int32_t bk = rdl(back, l);
             m.len = best;
             m.start = q - bk;
-            m.pos = hc_rdl(mine, l) - bk;
+            m.pos = rdl(mine, l) - bk;
             if (best == lim + q - low) break;   // nothing longer exists
         }
     }
     return m;
 }
 
-__device__ __forceinline__ int32_t hc_ext_bytes(int32_t v) { return v >= 15 ? 1 + (v - 15) / 255 : 0; }
-
-// the e = hc_ext_bytes(v) length bytes of v at o
+// the e = ext_len<true>(v) length bytes of v at o
 __device__ __forceinline__ void hc_put_ext(uint8_t* o, int32_t v, int32_t e, uint32_t lane) {
     if (e == 0) return;
     for (int32_t k = (int32_t)lane; k < e - 1; k += kWave) o[k] = 255;
@@ -279,7 +262,7 @@ __device__ __forceinline__ void hc_put_ext(uint8_t* o, int32_t v, int32_t e, uin
 // False (nothing written) if it does not fit in cap.
 __device__ __forceinline__ bool hc_emit(uint8_t* dst, int32_t& op, int32_t cap, const uint8_t* src, int32_t anchor,
                                         int32_t ll, int32_t off, int32_t ml, uint32_t lane) {
-    const int32_t le = hc_ext_bytes(ll), me = ml ? hc_ext_bytes(ml - 4) : 0;
+    const int32_t le = ext_len<true>(ll), me = ml ? ext_len<true>(ml - 4) : 0;
     const int64_t need = 1 + (int64_t)le + ll + (ml ? 2 + me : 0);
     if ((int64_t)op + need > (int64_t)cap) return false;
     uint8_t* o = dst + op;

@@ -42,14 +42,12 @@ namespace lz4m {
 
 constexpr uint32_t kEmpty = 0xFFFFu;
 
-// hash of 4 bytes into HB bits (LZ4_hash4, lz4.c:756-762: 13 bits for the
-// byU16 table).  The table is the kernel's whole LDS, and the kernel is
+// Positions are hashed by hash4<HB> (13 bits for the reference's byU16
+// table).  The table is the kernel's whole LDS, and the kernel is
 // latency bound: a 12-bit table (8 KB) fits 20 waves per CU instead of 10
 // and compresses 1.7x faster for +1.5 % size on the silesia-like mix
 // (LZ4M_PARSE_PARALLEL); 13 bits (LZ4M_PARSE_PARALLEL_HQ) keeps the
 // reference's table size and ratio (-0.02 %).
-template <int HB>
-__device__ __forceinline__ uint32_t phash(uint32_t v) { return (v * 2654435761u) >> (32 - HB); }
 
 // equal leading bytes of two 16-byte windows (0..16), branch-free: v_ffbl
 // gives ~0u for a zero word, so OR-ing the word's bit base (32 / 64 / 96)
@@ -70,8 +68,6 @@ __device__ __forceinline__ uint32_t eq_prefix16(u32x4 a, u32x4 b) {
     const uint32_t m = __builtin_elementwise_min(__builtin_elementwise_min(f0, f1), __builtin_elementwise_min(f2, f3));
     return m >= 128u ? 16u : m >> 3;
 }
-
-__device__ __forceinline__ int32_t rdl(int32_t v, int l) { return __builtin_amdgcn_readlane(v, l); }
 
 // Mask of the lanes whose HB-bit hash equals this lane's (active lanes only):
 // AND over the hash bits of "same bit" masks, each from one wave ballot.
@@ -94,55 +90,6 @@ __device__ __forceinline__ uint64_t same_hash_mask(uint32_t h, bool act) {
     }
     return ((uint64_t)hi << 32) | lo;
 }
-
-// y / 255 for y >= 0.  Blocks <= 64 KiB: (z + z/256) / 256 with z = y + 1,
-// exact for y < 65 790 (checked exhaustively), two shifts and two adds where
-// the division is a quarter-rate v_mul_hi_u32
-template <bool BIG>
-__device__ __forceinline__ int32_t div255(int32_t y) {
-    if (BIG) return y / 255;
-    const int32_t z = y + 1;
-    return (z + (z >> 8)) >> 8;
-}
-
-// length bytes after the token for a length field x (0 below 15)
-template <bool BIG>
-__device__ __forceinline__ int32_t ext_len(int32_t x) { return x >= 15 ? 1 + div255<BIG>(x - 15) : 0; }
-
-// inclusive prefix sum across the wave: row_shr 1/2/4/8 inside 16-lane rows,
-// then row_bcast:15 / row_bcast:31 carry the row totals (VALU only)
-__device__ __forceinline__ int32_t wave_incl_sum(int32_t v) {
-    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, false);   // row_shr:1
-    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, false);   // row_shr:2
-    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, false);   // row_shr:4
-    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, false);   // row_shr:8
-    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, false);   // row_bcast:15 -> rows 1, 3
-    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, false);   // row_bcast:31 -> rows 2, 3
-    return v;
-}
-
-// inclusive prefix max across the wave (v >= 0), as wave_incl_sum
-__device__ __forceinline__ int32_t wave_incl_max(int32_t v) {
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, false));   // row_shr:1
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, false));   // row_shr:2
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, false));   // row_shr:4
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, false));   // row_shr:8
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, false));   // row_bcast:15 -> rows 1, 3
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, false));   // row_bcast:31 -> rows 2, 3
-    return v;
-}
-
-// OR of v over the wave (uniform): inclusive prefix OR as wave_incl_sum, read at lane 63
-__device__ __forceinline__ uint32_t wave_or(uint32_t v) {
-    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, false);   // row_shr:1
-    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, false);   // row_shr:2
-    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, false);   // row_shr:4
-    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, false);   // row_shr:8
-    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false);   // row_bcast:15 -> rows 1, 3
-    v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false);   // row_bcast:31 -> rows 2, 3
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
-}
-
 
 // set bits of m in lanes below this one
 __device__ __forceinline__ int32_t count_below(uint64_t m) {
@@ -319,7 +266,7 @@ __device__ __forceinline__ void chunk_issue(Chunk& C, const uint8_t* s, uint32_t
     constexpr bool U32 = BIG && !WIN;   // whole positions in a u32 table
     const int32_t p = p0 + (int32_t)lane;
     const bool act = p + 4 <= N;
-    const uint32_t h = act ? phash<HB>(v) : (1u << HB);
+    const uint32_t h = act ? hash4<HB>(v) : (1u << HB);
     // lanes with the same hash (one ballot per hash bit), hence the nearest
     // earlier one (the candidate) and whether a later one exists (then this
     // lane does not write the table)
@@ -616,9 +563,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((BIG && !WIN
     }
 }
 
-// len bytes from s to d by the wave, 16 per lane, four loads in flight
-__device__ __forceinline__ void wave_copy(uint8_t* __restrict__ d, const uint8_t* __restrict__ s, int32_t len,
-                                          uint32_t lane) {
+// len bytes from s to d by the wave, 16 per lane, four loads in flight.  Not
+// wave_copy_wild: exactly len bytes (the next segment's output follows them).
+__device__ __forceinline__ void stitch_copy(uint8_t* __restrict__ d, const uint8_t* __restrict__ s, int32_t len,
+                                            uint32_t lane) {
     int32_t x = 16 * (int32_t)lane;
     for (; x + 3 * 1024 + 16 <= len; x += 4 * 1024) {
         const u32x4 a = ld16(s + x), b = ld16(s + x + 1024), c = ld16(s + x + 2048), e = ld16(s + x + 3072);
@@ -692,9 +640,9 @@ __global__ __launch_bounds__(64) void pcompress_stitch_kernel(const uint8_t* __r
             uint8_t* q = d + F;
             for (int32_t x = (int32_t)lane; x <= E; x += 64)
                 q[x] = (uint8_t)(x == 0 ? tok : x < E ? 255u : (uint32_t)(L - 15 - 255 * (E - 1)));
-            wave_copy(q + 1 + E, s + ck, L, lane);
+            stitch_copy(q + 1 + E, s + ck, L, lane);
             const int32_t h0 = 1 + ext_len<true>(l0) + l0;   // the slot's own first token, length bytes, literals
-            wave_copy(q + 1 + E + L, slots + (b * segs + k) * seg_cap + h0, o - h0, lane);
+            stitch_copy(q + 1 + E + L, slots + (b * segs + k) * seg_cap + h0, o - h0, lane);
         }
         if (lane == 0) out_len[b] = total;
     }

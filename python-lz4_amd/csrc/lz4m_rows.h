@@ -17,6 +17,9 @@ struct RowMeta {
     int64_t pad1;
 };
 static_assert(sizeof(RowMeta) == 32, "RowMeta layout");
+// ip == kRowsWholeLiteral: the block is already decoded (a whole-literal
+// block, copied by rows_parse_kernel) and op holds its size
+constexpr int32_t kRowsWholeLiteral = -1;
 
 // scratch layout: 64 bytes of counters, one RowMeta per block, then the
 // length bytes

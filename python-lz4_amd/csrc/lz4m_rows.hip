@@ -32,8 +32,6 @@
 #include "lz4m_common.h"
 #include "lz4m_rows.h"
 
-#include <limits.h>
-
 namespace lz4m {
 typedef __attribute__((address_space(3))) u32x4 lds_u32x4;
 
@@ -43,13 +41,7 @@ __device__ __forceinline__ void wait_vm0() { __builtin_amdgcn_s_waitcnt(0x0F70);
 // ------------------------------------------------------------- row helpers
 // A row = 16 consecutive lanes; DPP row_shr stays inside a row and
 // row_newbcast:n (gfx90a+) broadcasts lane n of each row to the whole row.
-__device__ __forceinline__ int32_t row_incl_sum(int32_t v) {
-    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, false);   // row_shr:1
-    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, false);   // row_shr:2
-    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, false);   // row_shr:4
-    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, false);   // row_shr:8
-    return v;
-}
+// (row_incl_sum is lz4m_common.h's.)
 // two inclusive row prefix sums at once (the chains interleave: no wait
 // states between dependent DPP steps)
 __device__ __forceinline__ void row_incl_sum2(int32_t& a, int32_t& b) {
@@ -64,25 +56,6 @@ __device__ __forceinline__ void row_incl_sum2(int32_t& a, int32_t& b) {
 }
 __device__ __forceinline__ int32_t row_last(int32_t v) { return __builtin_amdgcn_update_dpp(0, v, 0x15F, 0xF, 0xF, false); }
 __device__ __forceinline__ int32_t row_first(int32_t v) { return __builtin_amdgcn_update_dpp(0, v, 0x150, 0xF, 0xF, false); }
-
-// max of v over the lanes below in the row (-1 for lane 0); v >= -1
-__device__ __forceinline__ int32_t row_excl_max(int32_t v) {
-    int32_t x = __builtin_amdgcn_update_dpp(-1, v, 0x111, 0xF, 0xF, false);
-    x = max(x, __builtin_amdgcn_update_dpp(-1, x, 0x111, 0xF, 0xF, false));
-    x = max(x, __builtin_amdgcn_update_dpp(-1, x, 0x112, 0xF, 0xF, false));
-    x = max(x, __builtin_amdgcn_update_dpp(-1, x, 0x114, 0xF, 0xF, false));
-    x = max(x, __builtin_amdgcn_update_dpp(-1, x, 0x118, 0xF, 0xF, false));
-    return x;
-}
-// min of v over the lanes below in the row (INT_MAX for lane 0)
-__device__ __forceinline__ int32_t row_excl_min(int32_t v) {
-    int32_t x = __builtin_amdgcn_update_dpp(INT_MAX, v, 0x111, 0xF, 0xF, false);
-    x = min(x, __builtin_amdgcn_update_dpp(INT_MAX, x, 0x111, 0xF, 0xF, false));
-    x = min(x, __builtin_amdgcn_update_dpp(INT_MAX, x, 0x112, 0xF, 0xF, false));
-    x = min(x, __builtin_amdgcn_update_dpp(INT_MAX, x, 0x114, 0xF, 0xF, false));
-    x = min(x, __builtin_amdgcn_update_dpp(INT_MAX, x, 0x118, 0xF, 0xF, false));
-    return x;
-}
 
 // Two exclusive max-scans over the row at once (values >= 0, 0 = none):
 // max of a and of b over the lanes below (0 for lane 0).  Identity 0 lets
@@ -102,8 +75,10 @@ __device__ __forceinline__ void row_excl_max2(int32_t a, int32_t b, int32_t& xa,
     xb = y;
 }
 
-// Exactly k bytes (k >= 16: 16) of v at global address p.
-__device__ __forceinline__ void gbl_put(uint8_t* p, u32x4 v, int32_t k) {
+// Exactly k bytes (k >= 16: 16; k <= 0: none) of v at global address p.  gbl_put's
+// contract, kept apart: through gbl_put the compiler tests k's bits differently
+// here (compares, not masks) and rows_parse / rows_exec_kernel change.
+__device__ __forceinline__ void row_put(uint8_t* p, u32x4 v, int32_t k) {
     if (k >= 16) {
         st16(p, v);
         return;
@@ -166,7 +141,8 @@ typedef __attribute__((address_space(3))) volatile uint8_t lds_vu8;
 typedef __attribute__((address_space(3))) volatile uint32_t lds_vu32;
 constexpr int kPStage = 32;   // length ring (flushed in halves)
 constexpr int kPWG = 64;      // parse workgroup (LDS is allocated per workgroup)
-// a 64-bit address received from another lane, as a global pointer
+// a 64-bit address received from another lane, as a global pointer (readlane_ptr
+// reads a uniform lane; this address came by ds_bpermute, a lane per lane)
 __device__ __forceinline__ const uint8_t* readlane_safe_ptr(uint64_t a) {
     typedef __attribute__((address_space(1))) const uint8_t gu8;
     return (const uint8_t*)(gu8*)(uintptr_t)a;
@@ -198,7 +174,7 @@ __device__ __forceinline__ void load64(const uint8_t* s, int32_t x, int32_t iend
 // length <= oend.  The candidate lane f's block is checked here with those
 // tests (anything else is left to the finisher, as before) and its literal
 // copied by the wave, 8 KiB per round trip; the result is the decoded size
-// (-1: not such a block), which the lane records as meta ip = -1 (done), op =
+// (-1: not such a block), which the lane records as meta ip = kRowsWholeLiteral, op =
 // the size.  The copy overlaps the other waves' parsing, which is
 // latency-bound; in the finisher it ran at the device's copy rate after the
 // row execution (~2.4 ms of the headline launch's 4 ms finisher).
@@ -237,7 +213,7 @@ __device__ __forceinline__ int64_t whole_literal_block(const uint8_t* s, int32_t
             if (p < Lf) st16(d + p, w[u]);
         }
     }
-    if ((uint32_t)L != Lf && lane == ((Lf >> 4) & 63u)) gbl_put(d + Lf, ld16_guarded(cs + Lf, (int32_t)L - (int32_t)Lf), (int32_t)L - (int32_t)Lf);
+    if ((uint32_t)L != Lf && lane == ((Lf >> 4) & 63u)) row_put(d + Lf, ld16_guarded(cs + Lf, (int32_t)L - (int32_t)Lf), (int32_t)L - (int32_t)Lf);
     return L;
 }
 
@@ -503,7 +479,7 @@ __global__ __launch_bounds__(kPWG) void rows_parse_kernel(const uint8_t* __restr
                 op += (int32_t)(lit + ml);
                 ++k;
             } else {   // the first sequence that is not good: the finisher resumes here
-                for (int32_t c = kf; c < k; c += 16) gbl_put(lens + loff + c, lds_ld16(stg + (c & (kPStage - 1))), k - c);
+                for (int32_t c = kf; c < k; c += 16) row_put(lens + loff + c, lds_ld16(stg + (c & (kPStage - 1))), k - c);
                 meta[idx] = RowMeta{loff, k, ip - sh, op, 0, 0};
                 live = false;
             }
@@ -515,7 +491,7 @@ __global__ __launch_bounds__(kPWG) void rows_parse_kernel(const uint8_t* __restr
             const int32_t fsh = __builtin_amdgcn_readlane(sh, f);
             const int64_t r = whole_literal_block(readlane_ptr(s, f) + fsh, __builtin_amdgcn_readlane(iend, f) - fsh,
                                                   __builtin_amdgcn_readlane(oend, f), dst + dst_off[fi], lane);
-            if ((int)lane == f && r >= 0) meta[idx] = RowMeta{loff, 0, -1, (int32_t)r, 0, 0};
+            if ((int)lane == f && r >= 0) meta[idx] = RowMeta{loff, 0, kRowsWholeLiteral, (int32_t)r, 0, 0};
         }
         // flush full halves of the length ring
         if (live && k - kf >= kPStage / 2) {
@@ -625,11 +601,12 @@ constexpr int32_t kRowsRoom = 512;         // rebase when less room than this is
 constexpr int32_t kRowsKeep = kRowsH - kRowsRoom;   // history kept on a rebase
 static_assert(kRowsKeep % 16 == 0 && kRowsKeep + kRowsRoom <= kRowsH && kRowsKeep + 16 <= 1024, "history split");
 
-// Row-cooperative exact copies in HBM (16 lanes, lane j = jj).
+// Row-cooperative exact copies in HBM.  Apart from the coop_copy_* of
+// lz4m_decompress.hip: 16 lanes (lane j = jj), one load in flight per literal piece.
 __device__ __forceinline__ void row_copy_literal(uint8_t* d, const uint8_t* s, int32_t len, int32_t jj) {
     for (int32_t pos = 16 * jj; pos < len; pos += 256) {
         const u32x4 v = len - pos >= 16 ? ld16(s + pos) : ld16_guarded(s + pos, len - pos);
-        gbl_put(d + pos, v, len - pos);
+        row_put(d + pos, v, len - pos);
     }
 }
 
@@ -649,7 +626,7 @@ __device__ __forceinline__ void row_copy_match(uint8_t* d, int32_t off, int32_t 
                     if (p0 + 256 * u < e) v[u] = ld16(d + p0 + 256 * u - off);
 #pragma unroll
                 for (int u = 0; u < 4; ++u)
-                    if (p0 + 256 * u < e) gbl_put(d + p0 + 256 * u, v[u], len - (p0 + 256 * u));
+                    if (p0 + 256 * u < e) row_put(d + p0 + 256 * u, v[u], len - (p0 + 256 * u));
             }
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
         }
@@ -657,16 +634,7 @@ __device__ __forceinline__ void row_copy_match(uint8_t* d, int32_t off, int32_t 
     }
     const u32x4 pat = period_pattern(ld16(d - off), (uint32_t)off);
     const int32_t step = 16 - (16 % off);
-    for (int32_t pos = step * jj; pos < len; pos += step * 16) gbl_put(d + pos, pat, len - pos);
-}
-
-// 32 bytes of block input at t (bytes at or past iend read as zero)
-__device__ __forceinline__ void load32(const uint8_t* s, int32_t t, int32_t iend, bool valid, u32x4& a, u32x4& b) {
-    a = u32x4{0, 0, 0, 0};
-    b = a;
-    if (!valid) return;
-    a = t + 16 <= iend ? ld16(s + t) : ld16_guarded(s + t, iend - t);
-    b = t + 32 <= iend ? ld16(s + t + 16) : ld16_guarded(s + t + 16, iend - t - 16);
+    for (int32_t pos = step * jj; pos < len; pos += step * 16) row_put(d + pos, pat, len - pos);
 }
 
 
@@ -884,7 +852,7 @@ __global__ __launch_bounds__(kEWG) __attribute__((amdgpu_waves_per_eu(5, 8))) vo
             sync = true;
         }
         if (sync && k0 >= nseq) {   // the block's good prefix is done: flush the rest exactly
-            for (int32_t c = F + cold_j16(jj); c < op; c += 256) gbl_put(d + c, lds_ld16(HB + (c - base)), op - c);
+            for (int32_t c = F + cold_j16(jj); c < op; c += 256) row_put(d + c, lds_ld16(HB + (c - base)), op - c);
             have = false;
             continue;
         }
@@ -952,7 +920,7 @@ __global__ __launch_bounds__(kEWG) __attribute__((amdgpu_waves_per_eu(5, 8))) vo
                 M += 4;
             }
             // the flush and the literal touch different bytes: one fence for both
-            for (int32_t c = F + cold_j16(jj); c < op; c += 256) gbl_put(d + c, lds_ld16(HB + (c - base)), op - c);
+            for (int32_t c = F + cold_j16(jj); c < op; c += 256) row_put(d + c, lds_ld16(HB + (c - base)), op - c);
             row_copy_literal(d + op, s + q, L, jj);
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
             row_copy_match(d + op + L, ofs, M, jj);
