@@ -172,6 +172,35 @@ int lz4m_compress_hc_batch(const uint8_t* d_src, const int64_t* d_src_off, const
                            int32_t* d_out_len, int64_t n, int level, void* d_work, size_t work_bytes,
                            lz4m_stream_t stream);
 
+/*
+ * The same compressor for blocks with history: what
+ * lz4.block.compress(mode="high_compression", dict=D) computes with
+ * LZ4_loadDictHC + LZ4_compress_HC_continue (_block.c:112-119), and what a
+ * linked LZ4 frame's HC block sees of the input before it.  Layout as in
+ * lz4m_compress_dict_batch: d_dict_len[i] >= 0 is the dictionary's full
+ * length, and its last min(d_dict_len[i], 65536) bytes (the prefix) must be
+ * stored immediately before block i in d_src.  Matches may start in the
+ * prefix (offsets up to 65535); the result decodes with
+ * LZ4_decompress_safe_usingDict over that prefix.  The parse is DESIGN.md
+ * section 9.5 (tests/hc_model/hc_model_prefix.c), NOT byte-identical to
+ * lz4hc.c.  d_dict_len[i] <= 0: no prefix, the bytes of
+ * lz4m_compress_hc_batch.  Three launches: the blocks whose prefix + length
+ * is at most 65536 bytes, those up to 131072 (a linked frame's 64 KiB blocks),
+ * the longer ones.  d_out_len, level and the stream order are as for
+ * lz4m_compress_hc_batch.  d_work: at least
+ * lz4m_compress_hc_workspace_size(n, max_len) bytes;
+ * lz4m_compress_hc_dict_workspace_size(n, max_len) bytes (256 KiB per block,
+ * at most 640 MiB) let the second launch run twice as many wavefronts, which
+ * is what its speed depends on.  The bytes produced do
+ * not depend on the workspace's size.  LZ4M_EINVAL: n < 0, a null d_dict_len,
+ * or a missing, odd or short workspace; n == 0 returns 0.
+ */
+size_t lz4m_compress_hc_dict_workspace_size(int64_t n, int32_t max_len);
+int lz4m_compress_hc_dict_batch(const uint8_t* d_src, const int64_t* d_src_off, const int32_t* d_src_len,
+                                const int32_t* d_dict_len, uint8_t* d_dst, const int64_t* d_dst_off,
+                                const int32_t* d_dst_cap, int32_t* d_out_len, int64_t n, int level,
+                                void* d_work, size_t work_bytes, lz4m_stream_t stream);
+
 /* Library identification (mirrors LZ4_versionNumber, lz4.c:728, of the
  * format version this codec is bit-compatible with: 10904). */
 int lz4m_version_number(void);

@@ -38,6 +38,13 @@
 //     comparisons are paid once per 64 candidates.
 // The kernel is bound by the latency of these dependent loads, so what counts
 // is the number of resident waves, which the head table decides (HcCfg).
+//
+// lz4m_compress_hc_dict_batch (hc_prefix_kernel) is the same parse for a block
+// with up to 64 KiB of history lying before it in memory (a dictionary's tail,
+// or the input before a linked frame's block): DESIGN.md section 9.5,
+// tests/hc_model/hc_model_prefix.c.  Positions then count from the start of
+// that prefix, which is inserted before the first search; the per-block body
+// (hc_block) is shared by both entry points.
 #include "lz4m_common.h"
 
 #include "../../include/lz4m.h"
@@ -48,25 +55,42 @@ namespace {
 constexpr int kHcHashBits = 13;
 constexpr int kHcHeads = 1 << kHcHashBits;
 constexpr int32_t kHcMaxDist = 65535;    // LZ4_DISTANCE_MAX
-constexpr int32_t kHcSmallMax = 65536;   // longest block of the u16-head kernel
+constexpr int32_t kHcSmallMax = 65536;   // longest prefix + block of kHcSmall (u16 heads hold position + 1)
+constexpr int32_t kHcPrefixMax = 65536;  // history bytes used in front of a block
 constexpr int32_t kHcMaxInput = 0x7E000000;
 
-// Two kernels share the parse.  Blocks up to 64 KiB: u16 heads (position + 1
+// Three configurations share the parse (M; false / true name the first two).
+// kHcSmall: blocks of up to 64 KiB, prefix included: u16 heads (position + 1
 // <= 65525; 16 KiB of LDS, 10 workgroups per CU of 160 KiB) and a chain
-// indexed by the position.  Longer blocks: u32 heads (32 KiB, 5 per CU) and a
-// chain of 2 x 65536 entries indexed by the position mod 131072: positions
-// are inserted up to 127 ahead of a search, and a window of exactly 65536
-// entries would overwrite that search's oldest candidates.
-template <bool BIG>
+// indexed by the position.  kHcBig: u32 heads (32 KiB, 5 per CU) and a chain
+// of 2 x 65536 entries indexed by the position mod 131072: positions are
+// inserted up to 127 ahead of a search, and a window of exactly 65536 entries
+// would overwrite that search's oldest candidates.  kHcRebased (prefix kernel
+// only): prefix + block of 65537..131072 bytes, the 64 KiB block of a linked
+// frame; u16 heads again, holding (position mod 65535) + 1, with kHcBig's
+// chain.  Such an entry names the positions d, d + 65535, ... back (d in
+// 1..65535), of which only the first is within LZ4_DISTANCE_MAX; it is the
+// newest position with the hash exactly when its four bytes hash to it (a
+// nearer position with that hash would have replaced the entry), which
+// insertion checks, so the chain is the one kHcBig builds.
+constexpr int kHcSmall = 0, kHcBig = 1, kHcRebased = 2;
+constexpr int32_t kHcRebasedMax = 131072;   // longest prefix + block of kHcRebased
+template <int M>
 struct HcCfg {
     typedef uint16_t head_t;
     static constexpr int kWaves = 2560;
     static constexpr uint32_t kChain = 65536;
 };
 template <>
-struct HcCfg<true> {
+struct HcCfg<kHcBig> {
     typedef uint32_t head_t;
     static constexpr int kWaves = 1280;
+    static constexpr uint32_t kChain = 131072;
+};
+template <>
+struct HcCfg<kHcRebased> {
+    typedef uint16_t head_t;
+    static constexpr int kWaves = 2560;   // as many of them as the caller's workspace has slices for
     static constexpr uint32_t kChain = 131072;
 };
 // both kernels' slices fill the same workspace (they run one after the other)
@@ -87,10 +111,15 @@ __device__ __forceinline__ void hc_st(T* p, uint32_t v) {
 __device__ __forceinline__ void hc_fence() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); }
 
 // The parse state of one block.  Everything is uniform across the wave.
-template <bool BIG>
+template <int M>
 struct HcBlock {
-    typedef __attribute__((address_space(3))) typename HcCfg<BIG>::head_t head_t;
-    static constexpr uint32_t kMask = HcCfg<BIG>::kChain - 1u;
+    typedef __attribute__((address_space(3))) typename HcCfg<M>::head_t head_t;
+    static constexpr uint32_t kMask = HcCfg<M>::kChain - 1u;
+
+    // kHcRebased: position (< 131072) mod 65535
+    static __device__ __forceinline__ uint32_t rebased(uint32_t p) {
+        return p >= 131070u ? p - 131070u : (p >= 65535u ? p - 65535u : p);
+    }
 
     head_t* head;
     uint16_t* chain;
@@ -122,11 +151,18 @@ struct HcBlock {
             if (act) {
                 const uint64_t below = same & ((1ull << lane) - 1ull);
                 const uint64_t above = same & ~((2ull << lane) - 1ull);
-                const uint32_t prev = below ? (uint32_t)base + (63u - (uint32_t)__builtin_clzll(below)) + 1u
-                                            : hc_ld(head + h);
+                uint32_t prev = below ? (uint32_t)base + (63u - (uint32_t)__builtin_clzll(below)) + 1u
+                                      : hc_ld(head + h);
+                if (M == kHcRebased && !below && prev) {
+                    const uint32_t r = rebased((uint32_t)p), e = prev - 1u;
+                    const uint32_t back = r > e ? r - e : r + 65535u - e;   // 1..65535
+                    prev = back <= (uint32_t)p && hash4<kHcHashBits>(ld32(src + p - (int32_t)back)) == h
+                               ? (uint32_t)p + 1u - back
+                               : 0u;
+                }
                 const uint32_t d = prev ? (uint32_t)p + 1u - prev : 0u;
                 hc_st(chain + ((uint32_t)p & kMask), d > (uint32_t)kHcMaxDist ? 0u : d);
-                if (above == 0) hc_st(head + h, (uint32_t)p + 1u);
+                if (above == 0) hc_st(head + h, M == kHcRebased ? rebased((uint32_t)p) + 1u : (uint32_t)p + 1u);
             }
             hc_fence();
             inserted = end;
@@ -208,9 +244,9 @@ struct HcMatch {
 };
 
 // search(q, low); q is inserted.  All values uniform.
-template <bool BIG>
-__device__ __forceinline__ HcMatch hc_search(HcBlock<BIG>& s, int32_t q, int32_t low) {
-    constexpr uint32_t kMask = HcBlock<BIG>::kMask;
+template <int M>
+__device__ __forceinline__ HcMatch hc_search(HcBlock<M>& s, int32_t q, int32_t low) {
+    constexpr uint32_t kMask = HcBlock<M>::kMask;
     const uint8_t* src = s.src;
     const int32_t lim = s.n - 5 - q;
     HcMatch m{0, 0, 0};
@@ -285,7 +321,100 @@ __device__ __forceinline__ bool hc_emit(uint8_t* dst, int32_t& op, int32_t cap, 
     return true;
 }
 
-// BIG = false: the blocks of up to kHcSmallMax bytes; BIG = true: the longer ones.
+// One block, parsed by one wave: the n bytes at base + P, whose history is the
+// P bytes before them (P = 0: section 9.1).  Positions
+// count from `base`, so the block is [P, P + n); the prefix is inserted ahead
+// of the first search like any other position below it, matches may start in
+// it, and no emitted sequence does (anchor >= P).  Returns the block's size,
+// or 0 if it does not fit in cap.  s.head, s.chain, s.attempts and s.lane are
+// set by the caller.
+template <int M>
+__device__ __forceinline__ int32_t hc_block(HcBlock<M>& s, const uint8_t* base, int32_t P, int32_t n, uint8_t* dst,
+                                            int32_t cap) {
+    const uint32_t lane = s.lane;
+    const int32_t total = P + n;
+    int32_t op = 0, anchor = P;
+    bool fits = true;
+    if (n >= 13) {
+        for (int32_t i = (int32_t)lane; i < kHcHeads; i += kWave) hc_st(s.head + i, 0u);
+        hc_fence();
+        const int32_t mflimit = total - 12;
+        s.src = base;
+        s.n = total;
+        s.ilimit = mflimit + 1;
+        s.inserted = 0;
+        if (P > 0) s.insert_through(P - 1);
+        int32_t ip = P;
+        while ((ip = s.next_candidate(ip, mflimit)) <= mflimit) {
+            HcMatch m = hc_search(s, ip, anchor);
+            if (m.len == 0) {
+                ++ip;
+                continue;
+            }
+            for (;;) {   // probe the end of the match for a longer one that overlaps it
+                const int32_t q = m.start + m.len - 2;
+                if (q > mflimit) break;
+                s.insert_through(q);
+                const HcMatch m2 = hc_search(s, q, m.start);
+                if (m2.len <= m.len) break;
+                if (m2.start - m.start >= 4) {   // keep the head of the first match
+                    fits = hc_emit(dst, op, cap, base, anchor, m.start - anchor, m.start - m.pos,
+                                   m2.start - m.start, lane);
+                    if (!fits) break;
+                    anchor = m2.start;
+                }
+                m = m2;
+            }
+            if (fits) fits = hc_emit(dst, op, cap, base, anchor, m.start - anchor, m.start - m.pos, m.len, lane);
+            if (!fits) break;
+            ip = m.start + m.len;
+            anchor = ip;
+        }
+    }
+    if (fits) fits = hc_emit(dst, op, cap, base, anchor, total - anchor, 0, 0, lane);
+    return fits ? op : 0;
+}
+
+// The persistent grid of both entry points: wave blockIdx.x takes every
+// gridDim.x-th block of the batch.  dict_len == nullptr (known at compile time
+// in hc_compress_kernel): no block has a prefix.  Configuration kHcSmall takes
+// the blocks whose prefix + length is at most kHcSmallMax bytes, kHcRebased
+// (with a prefix only) those up to kHcRebasedMax, kHcBig the others.
+template <int M, bool PREFIX>
+__device__ __forceinline__ void hc_grid(const uint8_t* __restrict__ src_base, const int64_t* __restrict__ src_off,
+                                        const int32_t* __restrict__ src_len, const int32_t* __restrict__ dict_len,
+                                        uint8_t* __restrict__ dst_base, const int64_t* __restrict__ dst_off,
+                                        const int32_t* __restrict__ dst_cap, int32_t* __restrict__ out_len,
+                                        int64_t nblocks, int32_t attempts, uint16_t* __restrict__ work) {
+    typedef typename HcCfg<M>::head_t head_mem_t;
+    __shared__ __attribute__((aligned(16))) head_mem_t head_mem[kHcHeads];
+    HcBlock<M> s;
+    s.head = (typename HcBlock<M>::head_t*)head_mem;
+    s.chain = work + (size_t)blockIdx.x * HcCfg<M>::kChain;
+    s.attempts = attempts;
+    s.lane = threadIdx.x;
+    for (int64_t b = blockIdx.x; b < nblocks; b += gridDim.x) {
+        const int32_t n = src_len[b];
+        int32_t P = 0;
+        if (PREFIX) {
+            const int32_t dl = dict_len[b];
+            P = dl < 0 ? 0 : (dl < kHcPrefixMax ? dl : kHcPrefixMax);
+        }
+        // (a negative n is refused below by either kernel; the small one takes it)
+        const int64_t total = (int64_t)P + (n < 0 ? 0 : n);
+        const int mine = total <= kHcSmallMax ? kHcSmall : (PREFIX && total <= kHcRebasedMax ? kHcRebased : kHcBig);
+        if (mine != M) continue;   // another kernel's block
+        const int32_t cap = dst_cap[b];
+        if (n < 0 || n > kHcMaxInput || cap < 0) {
+            if (s.lane == 0) out_len[b] = 0;
+            continue;
+        }
+        const int32_t r = hc_block<M>(s, src_base + src_off[b] - P, P, n, dst_base + dst_off[b], cap);
+        if (s.lane == 0) out_len[b] = r;
+    }
+}
+
+// lz4m_compress_hc_batch's kernels (no prefix)
 template <bool BIG>
 __global__ __launch_bounds__(64) void hc_compress_kernel(const uint8_t* __restrict__ src_base,
                                                          const int64_t* __restrict__ src_off,
@@ -295,64 +424,24 @@ __global__ __launch_bounds__(64) void hc_compress_kernel(const uint8_t* __restri
                                                          const int32_t* __restrict__ dst_cap,
                                                          int32_t* __restrict__ out_len, int64_t nblocks,
                                                          int32_t attempts, uint16_t* __restrict__ work) {
-    typedef typename HcCfg<BIG>::head_t head_mem_t;
-    __shared__ __attribute__((aligned(16))) head_mem_t head_mem[kHcHeads];
-    HcBlock<BIG> s;
-    s.head = (typename HcBlock<BIG>::head_t*)head_mem;
-    s.chain = work + (size_t)blockIdx.x * HcCfg<BIG>::kChain;
-    s.attempts = attempts;
-    s.lane = threadIdx.x;
-    const uint32_t lane = s.lane;
-    for (int64_t b = blockIdx.x; b < nblocks; b += gridDim.x) {
-        const int32_t n = src_len[b];
-        if ((n > kHcSmallMax) != BIG) continue;   // the other kernel's block
-        const int32_t cap = dst_cap[b];
-        const uint8_t* src = src_base + src_off[b];
-        uint8_t* dst = dst_base + dst_off[b];
-        if (n < 0 || n > kHcMaxInput || cap < 0) {
-            if (lane == 0) out_len[b] = 0;
-            continue;
-        }
-        int32_t op = 0, anchor = 0;
-        bool fits = true;
-        if (n >= 13) {
-            for (int32_t i = (int32_t)lane; i < kHcHeads; i += kWave) hc_st(s.head + i, 0u);
-            hc_fence();
-            const int32_t mflimit = n - 12;
-            s.src = src;
-            s.n = n;
-            s.ilimit = mflimit + 1;
-            s.inserted = 0;
-            int32_t ip = 0;
-            while ((ip = s.next_candidate(ip, mflimit)) <= mflimit) {
-                HcMatch m = hc_search(s, ip, anchor);
-                if (m.len == 0) {
-                    ++ip;
-                    continue;
-                }
-                for (;;) {   // probe the end of the match for a longer one that overlaps it
-                    const int32_t q = m.start + m.len - 2;
-                    if (q > mflimit) break;
-                    s.insert_through(q);
-                    const HcMatch m2 = hc_search(s, q, m.start);
-                    if (m2.len <= m.len) break;
-                    if (m2.start - m.start >= 4) {   // keep the head of the first match
-                        fits = hc_emit(dst, op, cap, src, anchor, m.start - anchor, m.start - m.pos,
-                                       m2.start - m.start, lane);
-                        if (!fits) break;
-                        anchor = m2.start;
-                    }
-                    m = m2;
-                }
-                if (fits) fits = hc_emit(dst, op, cap, src, anchor, m.start - anchor, m.start - m.pos, m.len, lane);
-                if (!fits) break;
-                ip = m.start + m.len;
-                anchor = ip;
-            }
-        }
-        if (fits) fits = hc_emit(dst, op, cap, src, anchor, n - anchor, 0, 0, lane);
-        if (lane == 0) out_len[b] = fits ? op : 0;
-    }
+    hc_grid<BIG ? kHcBig : kHcSmall, false>(src_base, src_off, src_len, nullptr, dst_base, dst_off, dst_cap, out_len, nblocks, attempts,
+                                            work);
+}
+
+// lz4m_compress_hc_dict_batch's kernels: block b's history is the last
+// min(dict_len[b], 65536) bytes before it in src
+template <int M>
+__global__ __launch_bounds__(64) void hc_prefix_kernel(const uint8_t* __restrict__ src_base,
+                                                       const int64_t* __restrict__ src_off,
+                                                       const int32_t* __restrict__ src_len,
+                                                       const int32_t* __restrict__ dict_len,
+                                                       uint8_t* __restrict__ dst_base,
+                                                       const int64_t* __restrict__ dst_off,
+                                                       const int32_t* __restrict__ dst_cap,
+                                                       int32_t* __restrict__ out_len, int64_t nblocks,
+                                                       int32_t attempts, uint16_t* __restrict__ work) {
+    hc_grid<M, true>(src_base, src_off, src_len, dict_len, dst_base, dst_off, dst_cap, out_len, nblocks, attempts,
+                     work);
 }
 
 // lz4hc.c level table: levels below 1 mean 9; 1-2 -> 2 attempts, 3 -> 4, ...
@@ -373,6 +462,14 @@ extern "C" size_t lz4m_compress_hc_workspace_size(int64_t n, int32_t max_len) {
     const int64_t waves = n < HcCfg<false>::kWaves ? n : HcCfg<false>::kWaves;
     const size_t bytes = (size_t)waves * HcCfg<true>::kChain * sizeof(uint16_t);
     return bytes < kHcWorkMax ? bytes : kHcWorkMax;
+}
+
+extern "C" size_t lz4m_compress_hc_dict_workspace_size(int64_t n, int32_t max_len) {
+    using namespace lz4m;
+    if (n <= 0 || max_len < 0) return 0;
+    // a 256 KiB slice for every wave of the widest grid (kHcRebased)
+    const int64_t waves = n < HcCfg<kHcRebased>::kWaves ? n : HcCfg<kHcRebased>::kWaves;
+    return (size_t)waves * HcCfg<kHcRebased>::kChain * sizeof(uint16_t);
 }
 
 extern "C" int lz4m_compress_hc_batch(const uint8_t* d_src, const int64_t* d_src_off, const int32_t* d_src_len,
@@ -396,5 +493,38 @@ extern "C" int lz4m_compress_hc_batch(const uint8_t* d_src, const int64_t* d_src
     const uint32_t big_grid = (uint32_t)(n < HcCfg<true>::kWaves ? n : HcCfg<true>::kWaves);
     hipLaunchKernelGGL(hc_compress_kernel<true>, dim3(big_grid), dim3(64), 0, st, d_src, d_src_off, d_src_len,
                        d_dst, d_dst_off, d_dst_cap, d_out_len, n, attempts, (uint16_t*)d_work);
+    return (int)hipGetLastError();
+}
+
+extern "C" int lz4m_compress_hc_dict_batch(const uint8_t* d_src, const int64_t* d_src_off, const int32_t* d_src_len,
+                                           const int32_t* d_dict_len, uint8_t* d_dst, const int64_t* d_dst_off,
+                                           const int32_t* d_dst_cap, int32_t* d_out_len, int64_t n, int level,
+                                           void* d_work, size_t work_bytes, lz4m_stream_t stream) {
+    using namespace lz4m;
+    if (n < 0) return LZ4M_EINVAL;
+    if (n == 0) return 0;
+    if (d_dict_len == nullptr || d_work == nullptr || ((uintptr_t)d_work & 1u) ||
+        work_bytes < lz4m_compress_hc_workspace_size(n, 0))
+        return LZ4M_EINVAL;
+    const int32_t attempts = hc_attempts(level);
+    hipStream_t st = (hipStream_t)stream;
+    // as above, one launch per configuration: prefix + length <= 64 KiB, <= 128 KiB, longer
+    const uint32_t small_grid = (uint32_t)(n < HcCfg<kHcSmall>::kWaves ? n : HcCfg<kHcSmall>::kWaves);
+    hipLaunchKernelGGL(hc_prefix_kernel<kHcSmall>, dim3(small_grid), dim3(64), 0, st, d_src, d_src_off, d_src_len,
+                       d_dict_len, d_dst, d_dst_off, d_dst_cap, d_out_len, n, attempts, (uint16_t*)d_work);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    // (a wave per 256 KiB slice the workspace holds: at least kHcBig's grid, twice that with
+    // lz4m_compress_hc_dict_workspace_size bytes)
+    int64_t slices = (int64_t)(work_bytes / (HcCfg<kHcRebased>::kChain * sizeof(uint16_t)));
+    if (slices > HcCfg<kHcRebased>::kWaves) slices = HcCfg<kHcRebased>::kWaves;
+    const uint32_t mid_grid = (uint32_t)(n < slices ? n : slices);
+    hipLaunchKernelGGL(hc_prefix_kernel<kHcRebased>, dim3(mid_grid), dim3(64), 0, st, d_src, d_src_off, d_src_len,
+                       d_dict_len, d_dst, d_dst_off, d_dst_cap, d_out_len, n, attempts, (uint16_t*)d_work);
+    e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    const uint32_t big_grid = (uint32_t)(n < HcCfg<kHcBig>::kWaves ? n : HcCfg<kHcBig>::kWaves);
+    hipLaunchKernelGGL(hc_prefix_kernel<kHcBig>, dim3(big_grid), dim3(64), 0, st, d_src, d_src_off, d_src_len,
+                       d_dict_len, d_dst, d_dst_off, d_dst_cap, d_out_len, n, attempts, (uint16_t*)d_work);
     return (int)hipGetLastError();
 }

@@ -63,6 +63,8 @@ def _declare(lib) -> None:
         "lz4m_compress_linked_batch": ([vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, vp, C.c_size_t, vp], i32),
         "lz4m_compress_hc_workspace_size": ([i64, i32], C.c_size_t),
         "lz4m_compress_hc_batch": ([vp, vp, vp, vp, vp, vp, vp, i64, i32, vp, C.c_size_t, vp], i32),
+        "lz4m_compress_hc_dict_workspace_size": ([i64, i32], C.c_size_t),
+        "lz4m_compress_hc_dict_batch": ([vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, vp, C.c_size_t, vp], i32),
         "lz4m_xxh32_batch": ([vp, vp, vp, u32, vp, i64, vp], i32),
         "lz4m_xxh32_long": ([vp, i64, u32, vp, vp], i32),
         "lz4m_scan_scratch_entries": ([i64], i64),
@@ -266,6 +268,28 @@ def launch_compress_hc(src, src_off, src_len, dst, dst_off, dst_cap, out_len, n,
     rc = L.lz4m_compress_hc_batch(ptr(src), ptr(src_off), ptr(src_len), ptr(dst), ptr(dst_off), ptr(dst_cap),
                                   ptr(out_len), n, level, ptr(work), work.numel(), stream_ptr(stream))
     check(rc, "lz4m_compress_hc_batch")
+
+
+def launch_compress_hc_dict(src, src_off, src_len, dict_len, dst, dst_off, dst_cap, out_len, n, level: int = 9,
+                            stream=None, max_len: int = 0) -> None:
+    """launch_compress_hc for blocks with history (lz4m_compress_hc_dict_batch):
+    the last min(dict_len[i], 65536) bytes of block i's dictionary precede it
+    in ``src`` (as for launch_compress_dict); dict_len[i] <= 0: no history.
+    The chain workspace (lz4m_compress_hc_dict_workspace_size: 256 KiB per
+    block, 640 MiB at most) is allocated per call on the stream that uses it."""
+    L = lib()
+    if n <= 0:
+        check(L.lz4m_compress_hc_dict_batch(None, None, None, None, None, None, None, None, n, level, None, 0,
+                                            stream_ptr(stream)), "lz4m_compress_hc_dict_batch")
+        return
+    s = stream if stream is not None else torch.cuda.current_stream(src.device)
+    with torch.cuda.stream(s):
+        work = torch.empty(int(L.lz4m_compress_hc_dict_workspace_size(n, max_len)), dtype=torch.uint8,
+                           device=src.device)
+    rc = L.lz4m_compress_hc_dict_batch(ptr(src), ptr(src_off), ptr(src_len), ptr(dict_len), ptr(dst), ptr(dst_off),
+                                       ptr(dst_cap), ptr(out_len), n, level, ptr(work), work.numel(),
+                                       stream_ptr(stream))
+    check(rc, "lz4m_compress_hc_dict_batch")
 
 
 def launch_compress_linked(src, src_off, src_len, link, dst, dst_off, dst_cap, out_len, n, accel,

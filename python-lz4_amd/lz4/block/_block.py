@@ -127,8 +127,9 @@ def compress(source, mode="default", store_size=True, acceleration=1, compressio
     a valid block near the size of ``LZ4_compress_HC`` at that level, NOT
     byte-identical to it.  Levels below 1 mean 9; levels 10-12 and above
     search as level 9 (the reference's optimal parser is not built).  HC with
-    ``dict=`` (``LZ4_loadDictHC``) is not built and raises
-    ``NotImplementedError``.
+    ``dict=`` (``LZ4_loadDictHC``) raises ``NotImplementedError`` from this
+    call; ``compress_many(mode='high_compression', dict=D)`` and
+    ``compress_batch(dict_len=)`` compress with a dictionary.
     """
     src = _buffer(source)
     acceleration = _c_int(acceleration, "acceleration")
@@ -359,12 +360,13 @@ def compress_many(blocks, accel: int = 1, store_size: bool = True, as_bytearray:
     memory ends where each source begins (prefix mode, lz4.c:1671).
     ``mode="high_compression"``: the hash-chain compressor at level
     ``compression`` (valid blocks near LZ4_compress_HC's size, not
-    byte-identical; ``accel`` and ``table`` are ignored, ``dict`` is not
-    built)."""
+    byte-identical; ``accel``, ``table`` and ``dict_prefix`` are ignored).
+    With ``dict`` of any length (lz4m_compress_hc_dict_batch) matches may
+    reach into the dictionary's last 64 KiB, and the result decodes with
+    ``lz4.block.decompress(comp, dict=dict)``; an empty ``dict`` gives the
+    bytes of no ``dict``."""
     hc = _hc_mode(mode)
     compression = _c_int(compression, "compression")
-    if hc and dict is not None:
-        raise NotImplementedError("mode='high_compression' with dict= (LZ4_loadDictHC) is not built")
     views = [_buffer(b) for b in blocks]
     dev = N.device()
     n = len(views)
@@ -378,14 +380,19 @@ def compress_many(blocks, accel: int = 1, store_size: bool = True, as_bytearray:
         payload = views
     else:
         dv = _buffer(dict, "dict")
-        tail = dv[-65536:] if dv.nbytes >= 8 else dv[:0]   # LZ4_loadDict keeps the last 64 KiB (lz4.c:1568)
+        # LZ4_loadDict keeps the last 64 KiB (lz4.c:1568) and nothing of a dictionary below 8 bytes; HC keeps any
+        tail = dv[-65536:] if dv.nbytes >= 8 or hc else dv[:0]
         t = tail.nbytes
         offs = np.arange(1, n + 1, dtype=np.int64) * t + (np.concatenate([[0], np.cumsum(lens[:-1], dtype=np.int64)])
                                                             if n > 1 else np.zeros(1, np.int64))
         payload = [x for v in views for x in (tail, v)]
     lay, h, d = _stage_in(dev, payload, offs, lens, d_off, caps)
     d_src, src_off, src_len, d_dst, dst_off, dst_cap, out_len = _dev_views(lay, d, n)
-    if hc:
+    if hc and dict is not None:
+        dict_len = torch.full((n,), dv.nbytes, dtype=torch.int32, device=dev)
+        N.launch_compress_hc_dict(d_src, src_off, src_len, dict_len, d_dst, dst_off, dst_cap, out_len, n, compression,
+                                  max_len=max(lens))
+    elif hc:
         N.launch_compress_hc(d_src, src_off, src_len, d_dst, dst_off, dst_cap, out_len, n, compression,
                              max_len=max(lens))
     elif dict is None:
@@ -498,7 +505,7 @@ def decompress_many(blocks, uncompressed_size=-1, dict=None, as_bytearray: bool 
 def compress_batch(src: torch.Tensor, src_off: torch.Tensor, src_len: torch.Tensor, *,
                    table: str | int = "block", acceleration: int = 1, dst: torch.Tensor | None = None,
                    dst_off: torch.Tensor | None = None, dst_cap: torch.Tensor | None = None, stream=None,
-                   mode: str = "default", compression: int = 9):
+                   mode: str = "default", compression: int = 9, dict_len: torch.Tensor | None = None):
     """Compress n device-resident blocks in one stream-ordered launch.
 
     ``src`` uint8 (HBM), ``src_off`` int64[n], ``src_len`` int32[n].
@@ -515,9 +522,16 @@ def compress_batch(src: torch.Tensor, src_off: torch.Tensor, src_len: torch.Tens
     mean 9, 3..9 search 4..256 chain candidates per position, levels 10-12
     and above search as 9 (the reference's optimal parser is not built).  A
     block that does not fit its slot reports 0; an exact fit is accepted.
+    ``dict_len`` int32[n] (this mode only, lz4m_compress_hc_dict_batch):
+    block i has a dictionary of dict_len[i] bytes whose last min(dict_len[i],
+    65536) bytes lie immediately before it in ``src``; matches may reach into
+    them, and the block decodes with those bytes as its dictionary.
+    dict_len[i] <= 0: no dictionary.
     """
     hc = _hc_mode(mode)
     compression = _c_int(compression, "compression")
+    if dict_len is not None and not hc:
+        raise ValueError("dict_len is only valid with mode='high_compression'")
     tab = {"block": N.TABLE_U32_HASH5, "default": N.TABLE_AUTO, "u16": N.TABLE_U16_HASH4}.get(table, table)
     n = src_off.numel()
     dev = src.device
@@ -530,7 +544,10 @@ def compress_batch(src: torch.Tensor, src_off: torch.Tensor, src_len: torch.Tens
         dst = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
     out_len = torch.empty(n, dtype=torch.int32, device=dev)
     if hc:
-        if n:
+        if n and dict_len is not None:
+            N.launch_compress_hc_dict(src, src_off, src_len, dict_len.to(torch.int32), dst, dst_off, dst_cap, out_len,
+                                      n, compression, stream)
+        elif n:
             N.launch_compress_hc(src, src_off, src_len, dst, dst_off, dst_cap, out_len, n, compression, stream)
     else:
         N.launch_compress(src, src_off, src_len, dst, dst_off, dst_cap, out_len, n, int(tab), int(acceleration),

@@ -213,6 +213,11 @@ def compress_device(d_src: torch.Tensor, n: int | None = None, *, compression_le
     frame is byte-identical to the reference's for independent blocks.
     parse="parallel": the parallel-parse compressor (valid blocks at the
     ratio of LZ4_compress_default, not byte-identical; BASELINE config 4).
+    parse="hc" with compression_level >= 3: the hash-chain compressor at that
+    level (valid blocks near LZ4F_compressFrame's size at the level, not
+    byte-identical).  A linked frame's blocks, each with the 64 KiB of input
+    before it as history, are compressed in one launch
+    (lz4m_compress_hc_dict_batch).
 
     The content checksum (one serial XXH32 stream over all of d_src) runs on
     a host core beside the block compression, over pipelined PCIe copies of
@@ -240,10 +245,13 @@ def _compress_frame(d_src, n=None, *, compression_level=0, block_size=0, content
     it is stored raw (None when the input is empty)."""
     n = d_src.numel() if n is None else int(n)
     level = int(compression_level)
-    if level >= 3:
+    if parse not in ("exact", "parallel", "hc"):
+        raise ValueError("parse must be 'exact', 'parallel' or 'hc'")
+    if parse == "hc":
+        if level < 3:
+            raise ValueError("parse='hc' needs compression_level >= 3 (levels 0-2 are the fast compressor)")
+    elif level >= 3:
         raise NotImplementedError("LZ4 HC compression levels (>= 3) are outside the MI355X codec's scope")
-    if parse not in ("exact", "parallel"):
-        raise ValueError("parse must be 'exact' or 'parallel'")
     accel = -level + 1 if level < 0 else 1                     # lz4frame.c:855
     bsid = _optimal_bsid(int(block_size), n)
     if bsid == 0:
@@ -285,7 +293,14 @@ def _compress_frame(d_src, n=None, *, compression_level=0, block_size=0, content
         cmp = torch.empty(nb * slot, dtype=torch.uint8, device=dev)
         cmp_off = torch.arange(nb, dtype=torch.int64, device=dev) * slot
         cmp_len = torch.empty(nb, dtype=torch.int32, device=dev)
-        if parse == "exact" and linked:   # one stream across the blocks (lz4frame.c:865-871)
+        if parse == "hc" and linked:
+            # block i's history is the input before it, at most 64 KiB: every block in one launch
+            N.launch_compress_hc_dict(d_src, raw_off, raw_len, raw_off.clamp(max=65536).to(torch.int32), cmp,
+                                      cmp_off, cap, cmp_len, nb, level, stream, max_len=bsize)
+        elif parse == "hc":
+            N.launch_compress_hc(d_src, raw_off, raw_len, cmp, cmp_off, cap, cmp_len, nb, level, stream,
+                                 max_len=bsize)
+        elif parse == "exact" and linked:   # one stream across the blocks (lz4frame.c:865-871)
             link = torch.ones(nb, dtype=torch.int32, device=dev)
             link[0] = 0
             mode = N.LINKED_SPECULATIVE if nb >= _SPEC_MIN_BLOCKS else N.LINKED_SERIAL
