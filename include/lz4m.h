@@ -243,7 +243,7 @@ size_t lz4m_decompress_workspace_size(int64_t n, int64_t src_bytes);
 /* lz4m_decompress_batch with caller-provided device scratch (8-byte aligned,
  * at least lz4m_decompress_workspace_bytes(), not shared with a concurrently
  * running call).  Picks the decoder by batch size and scratch: rows from
- * LZ4M_ROWS_MIN_BLOCKS (32 768) blocks when the scratch fits, else hist
+ * 32 768 blocks when the scratch fits, else hist
  * (env LZ4M_DECODER=rows|hist forces one). */
 int lz4m_decompress_batch_ws(const uint8_t* d_src, const int64_t* d_src_off, const int32_t* d_src_len,
                              uint8_t* d_dst, const int64_t* d_dst_off, const int32_t* d_dst_cap,

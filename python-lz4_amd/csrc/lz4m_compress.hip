@@ -1481,12 +1481,6 @@ extern "C" int lz4m_compress_prefix_batch(const uint8_t* d_src, const int64_t* d
                                 acceleration, 1, stream);
 }
 
-extern "C" int lz4m_compress_prof(unsigned long long* out, int reset) {
-    (void)out;
-    (void)reset;
-    return -1;
-}
-
 static thread_local int g_linked_passes = 0;
 extern "C" int lz4m_compress_linked_passes(void) { return g_linked_passes; }
 

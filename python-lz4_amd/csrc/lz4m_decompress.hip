@@ -1205,11 +1205,9 @@ int current_device() {
     return dev >= 0 && dev < 64 ? dev : 0;
 }
 
-int env_int(const char* name, int dflt) {
-    const char* e = getenv(name);
-    const int v = e != nullptr ? atoi(e) : 0;
-    return v > 0 ? v : dflt;
-}
+// smallest batch the row decoder takes when the caller leaves the choice
+// open (crossover measured)
+constexpr int kRowsMinBlocks = 32768;
 
 // the values are the C-ABI's decoder ids (include/lz4m.h); 1, 2, 5 and 6
 // were retired decoders and are rejected
@@ -1253,9 +1251,7 @@ extern "C" int lz4m_decompress_batch_sel(const uint8_t* d_src, const int64_t* d_
     // sequence lengths (lz4m_decompress_workspace_size); without it (or for
     // small batches) the one-wavefront-per-block decoder takes any batch
     const bool rows_fit = work_bytes >= lz4m_rows_fixed_bytes(n) + 64;
-    // LZ4M_ROWS_MIN_BLOCKS: smallest batch sent to the row decoder (tuning)
-    static const int rows_min = env_int("LZ4M_ROWS_MIN_BLOCKS", 32768);   // crossover measured, DESIGN 3.1
-    if (decoder == kAuto) decoder = rows_fit && n >= rows_min ? kRowsDec : kHistDec;
+    if (decoder == kAuto) decoder = rows_fit && n >= kRowsMinBlocks ? kRowsDec : kHistDec;
     if (decoder != kHistDec && !rows_fit) decoder = kHistDec;
     if (decoder == kRowsDec) {
         int pg = 1, eg = 1;

@@ -19,8 +19,6 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "_lz4m.so")
-if os.environ.get("LZ4M_LIB"):   # dev hook: an alternative build of the same library (A/B runs)
-    LIB_PATH = os.environ["LZ4M_LIB"]
 
 TABLE_U16_HASH4 = 0
 TABLE_U32_HASH5 = 1
@@ -222,9 +220,9 @@ def launch_compress(src, src_off, src_len, dst, dst_off, dst_cap, out_len, n, ta
                     max_len: int | None = None) -> None:
     """Batched compression (lz4m_compress_batch).  PARSE_PARALLEL_LARGE with
     ``max_len`` (the longest block) parses each block as up to 16 segments
-    (lz4m_pcompress_large_batch; LZ4M_PC_SEG=0: one wavefront per block)."""
+    (lz4m_pcompress_large_batch)."""
     L = lib()
-    if table == PARSE_PARALLEL_LARGE and max_len is not None and os.environ.get("LZ4M_PC_SEG", "1") != "0":
+    if table == PARSE_PARALLEL_LARGE and max_len is not None:
         s = stream if stream is not None else torch.cuda.current_stream(src.device)
         with torch.cuda.stream(s):   # (allocated on the stream that uses it)
             work = torch.empty(int(L.lz4m_pcompress_large_workspace_size(n, max_len)), dtype=torch.uint8,
@@ -410,51 +408,26 @@ def _pinned_release(chunk: int, bufs) -> None:
         _PIN.setdefault(chunk, []).append(bufs)
 
 
+# The hashing copies run on a high-priority stream: HIP multiplexes
+# same-priority streams over a few hardware queues (GPU_MAX_HW_QUEUES), and
+# a copy stream on the compressing stream's queue ran its copies after the
+# kernel -- the config-4 frame with a content checksum measured 8.4 GiB/s in
+# the full bench, 11.9 with this
+_HASH_STREAM_PRIORITY = -1
+
 def xxh32_of_device(t: torch.Tensor, n: int, seed: int = 0, wait_stream=None, chunk: int = 64 << 20,
                     wait_event=None) -> int:
-    """XXH32 of the first n bytes of a device tensor, hashed on a host core:
-    chunks are copied to two pinned buffers on a side stream, each hashed
-    while the next one copies (PCIe ~50 GB/s against ~13 GB/s of hashing).
+    """XXH32 of the first n bytes of a device tensor, hashed on a host core
+    (xxh32_of_device_spans over the one span [0, n)).
     ``wait_event``: an event recorded when t was ready (preferred: a caller
     running this in a thread records it before queueing more work), else
     ``wait_stream``: the stream that produced t (default: current)."""
-    st = HostXXH32(seed)
     if n <= 0:
-        return st.digest()
-    dev = t.device
-    # a high-priority copy stream (LZ4M_HASH_STREAM_PRIORITY, default -1):
-    # HIP multiplexes same-priority streams over a few hardware queues
-    # (GPU_MAX_HW_QUEUES), and a copy stream on the compressing stream's
-    # queue ran its copies after the kernel -- the config-4 frame with a
-    # content checksum measured 8.4 GiB/s in the full bench, 11.9 with this
-    side = torch.cuda.Stream(dev, priority=int(os.environ.get("LZ4M_HASH_STREAM_PRIORITY", "-1")))
-    if wait_event is not None:
-        side.wait_event(wait_event)
-    else:
-        side.wait_stream(wait_stream if wait_stream is not None else torch.cuda.current_stream(dev))
-    bufs = _pinned_pair(chunk)
-    evs = [torch.cuda.Event(), torch.cuda.Event()]
-    spans = [(lo, min(n, lo + chunk)) for lo in range(0, n, chunk)]
-    flat = t.view(-1)
-
-    def issue(i):
-        lo, hi = spans[i]
-        with torch.cuda.stream(side):
-            bufs[i & 1][: hi - lo].copy_(flat[lo:hi], non_blocking=True)
-            evs[i & 1].record(side)
-
-    try:
-        issue(0)
-        for i, (lo, hi) in enumerate(spans):
-            if i + 1 < len(spans):
-                issue(i + 1)   # its buffer was hashed in iteration i - 1
-            evs[i & 1].synchronize()
-            st.update_ptr(bufs[i & 1].data_ptr(), hi - lo)
-    finally:
-        for e in evs:
-            e.synchronize()
-        _pinned_release(chunk, bufs)
-    return st.digest()
+        return HostXXH32(seed).digest()
+    if wait_event is None:
+        wait_event = torch.cuda.Event()
+        wait_event.record(wait_stream if wait_stream is not None else torch.cuda.current_stream(t.device))
+    return xxh32_of_device_spans(t, [(0, n, wait_event)], seed, chunk=chunk).digest()
 
 
 def xxh32_of_device_spans(t: torch.Tensor, spans, seed: int = 0, state: "HostXXH32 | None" = None,
@@ -462,9 +435,10 @@ def xxh32_of_device_spans(t: torch.Tensor, spans, seed: int = 0, state: "HostXXH
     """Continue an XXH32 on a host core over device bytes t[lo:hi] of each
     span (lo, hi, event) in order, the spans contiguous: a span's copies are
     queued behind its event (the device work that writes those bytes), so
-    the hash follows the producer instead of waiting for all of it.  Returns
-    the state (``.digest()`` ends it).  The copy and pinned-buffer scheme is
-    xxh32_of_device's."""
+    the hash follows the producer instead of waiting for all of it.  Chunks
+    are copied to two pinned buffers on a side stream, each hashed while the
+    next one copies (PCIe ~50 GB/s against ~13 GB/s of hashing).  Returns
+    the state (``.digest()`` ends it)."""
     st = state if state is not None else HostXXH32(seed)
     pieces = []
     for lo, hi, ev in spans:
@@ -473,7 +447,7 @@ def xxh32_of_device_spans(t: torch.Tensor, spans, seed: int = 0, state: "HostXXH
     if not pieces:
         return st
     dev = t.device
-    side = torch.cuda.Stream(dev, priority=int(os.environ.get("LZ4M_HASH_STREAM_PRIORITY", "-1")))
+    side = torch.cuda.Stream(dev, priority=_HASH_STREAM_PRIORITY)
     bufs = _pinned_pair(chunk)
     evs = [torch.cuda.Event(), torch.cuda.Event()]
     flat = t.view(-1)
@@ -492,7 +466,7 @@ def xxh32_of_device_spans(t: torch.Tensor, spans, seed: int = 0, state: "HostXXH
         issue(0)
         for i, (lo, hi, _ev) in enumerate(pieces):
             if i + 1 < len(pieces):
-                issue(i + 1)
+                issue(i + 1)   # its buffer was hashed in iteration i - 1
             evs[i & 1].synchronize()
             st.update_ptr(bufs[i & 1].data_ptr(), hi - lo)
     finally:

@@ -58,23 +58,12 @@ def _err(fn: str, code: str) -> RuntimeError:
     return RuntimeError(f"{fn} failed with code: ERROR_{code}")
 
 
-def _content_on_gpu() -> bool:
-    """LZ4M_CONTENT_XXH32=gpu runs the content checksum on one wavefront
-    (lz4m_xxh32_long, 1.7 GB/s) instead of a host core (A/B runs)."""
-    return os.environ.get("LZ4M_CONTENT_XXH32", "host") == "gpu"
-
-
 def _xxh32_dev(buf: bytes | memoryview | torch.Tensor, n: int | None = None, seed: int = 0) -> int:
     """XXH32 of a buffer: host bytes on this core; device bytes on a host
-    core over pipelined PCIe copies (or on the GPU, _content_on_gpu)."""
+    core over pipelined PCIe copies."""
     if not isinstance(buf, torch.Tensor):
         return N.xxh32_host(buf, seed)
-    length = n if n is not None else buf.numel()
-    if not _content_on_gpu():
-        return N.xxh32_of_device(buf, length, seed)
-    out = torch.empty(1, dtype=torch.int32, device=buf.device)
-    N.launch_xxh32_long(buf, length, seed, out)
-    return int(out.item()) & 0xFFFFFFFF
+    return N.xxh32_of_device(buf, n if n is not None else buf.numel(), seed)
 
 
 class _HashThread(threading.Thread):
@@ -102,7 +91,7 @@ class _HashThread(threading.Thread):
 # ------------------------------------------------------------------ header
 # linked frames with at least this many blocks compress speculatively in
 # parallel (lz4m_compress_linked_batch); shorter ones one wavefront per frame
-_SPEC_MIN_BLOCKS = int(os.environ.get("LZ4M_SPEC_MIN_BLOCKS", "4"))
+_SPEC_MIN_BLOCKS = 4
 
 
 def _optimal_bsid(requested: int, size: int) -> int:
@@ -268,15 +257,9 @@ def _compress_frame(d_src, n=None, *, compression_level=0, block_size=0, content
     body = None
     meta = None
     main = stream if stream is not None else torch.cuda.current_stream(dev)
-    h = hthread = None
+    hthread = None
     if content_checksum:                                       # lz4frame.c:1042, 1170-1176
-        if _content_on_gpu():
-            side = torch.cuda.Stream(dev)
-            side.wait_stream(main)
-            h = torch.empty(1, dtype=torch.int32, device=dev)
-            N.launch_xxh32_long(d_src, n, 0, h, side)
-            h.record_stream(main)
-        elif host_src is not None:   # the caller's bytes: hash them while the device compresses
+        if host_src is not None:     # the caller's bytes: hash them while the device compresses
             hthread = _HashThread(lambda: N.xxh32_host(host_src))
             hthread.start()
         else:                        # device bytes: streamed back and hashed while the device compresses
@@ -332,12 +315,8 @@ def _compress_frame(d_src, n=None, *, compression_level=0, block_size=0, content
     pos = len(hdr) + total
     out[pos: pos + 4] = 0                                      # endmark, lz4frame.c:1167
     if content_checksum:
-        if hthread is not None:
-            dig = hthread.result()
-            out[pos + 4: pos + 8] = torch.frombuffer(bytearray(struct.pack("<I", dig)), dtype=torch.uint8).to(dev)
-        else:
-            main.wait_stream(side)
-            out[pos + 4: pos + 8] = h.view(torch.uint8)
+        dig = hthread.result()
+        out[pos + 4: pos + 8] = torch.frombuffer(bytearray(struct.pack("<I", dig)), dtype=torch.uint8).to(dev)
     return out[: pos + tail], meta
 
 
@@ -409,18 +388,12 @@ def decompress(data, return_bytearray=False, return_bytes_read=False):
         out_t, total, first_err = _decode_records(*args)
     _frame_errors(first_err, state, info, total)
     bytes_read = state[1]
-    host_hash = info["content_checksum"] and not (total and _content_on_gpu())
-    got = None
-    if host_hash:   # on the copy the caller gets, hashed while it is staged (lz4frame.c:1850, :1959-1964)
+    if info["content_checksum"]:   # on the copy the caller gets, hashed while it is staged (lz4frame.c:1850, 1959-1964)
         out, got = N.to_host_bytes(out_t, total, bool(return_bytearray), hash_seed=0)
+        if got != struct.unpack_from("<I", mv, state[2])[0]:
+            raise _err("LZ4F_decompress", "contentChecksum_invalid")
     else:
         out = N.to_host_bytes(out_t, total, bool(return_bytearray))
-    if info["content_checksum"]:
-        want = struct.unpack_from("<I", mv, state[2])[0]
-        if got is None:
-            got = _xxh32_dev(out_t, total)
-        if got != want:
-            raise _err("LZ4F_decompress", "contentChecksum_invalid")
     if return_bytes_read:
         return out, bytes_read
     return out
@@ -486,7 +459,7 @@ def _decompress_pipelined(mv, info, recs, state, as_bytearray):
     total = info["content_size"]
     n = mv.nbytes
     if (state[0] != "end" or info["block_linked"] or nb < 32 or n < N._BIG
-            or not total or not ((nb - 1) * maxb < total <= nb * maxb) or _content_on_gpu()
+            or not total or not ((nb - 1) * maxb < total <= nb * maxb)
             or any(r[0] for r in recs)):
         return None
     dev = N.device()
@@ -654,8 +627,7 @@ def decompress_device(d_frame: torch.Tensor, n: int | None = None, stream=None) 
     if nb:
         crc_pos = rec_pos[:nb] + rec_len[:nb].to(torch.int64) if crc else torch.full((nb,), -1, dtype=torch.int64,
                                                                                       device=dev)
-        follow = bool(info["content_checksum"]) and not _content_on_gpu() and \
-            os.environ.get("LZ4M_FRAME_FOLLOW", "1") != "0"
+        follow = bool(info["content_checksum"])
         r = _decode_records(d_frame, info, nb, rec_pos[:nb], rec_len[:nb], rec_raw[:nb].to(torch.bool), crc_pos,
                             follow_hash=follow)
         out_t, total, first_err = r[:3]

@@ -261,6 +261,29 @@ def test_xxh32_long(gpu, oracle, corpus, n, shift):
         assert out.item() & 0xFFFFFFFF == oracle.xxh32(data, seed)
 
 
+@pytest.mark.parametrize("wait", ["event", "stream"])
+def test_xxh32_of_device(gpu, wait):
+    """The host-core hash of device bytes (xxh32_of_device, one span of
+    xxh32_of_device_spans) against the host hash of the same bytes, at the
+    sizes where the two-buffer alternation and the tail can go wrong around
+    a 4 096-byte chunk; the bytes are produced on a side stream that the hash
+    waits for through an event or through the stream itself."""
+    chunk = 4096
+    buf = np.random.default_rng(11).integers(0, 256, 2 * chunk + 3, dtype=np.uint8)
+    base = torch.from_numpy(buf).to(gpu)
+    s = torch.cuda.Stream(gpu)
+    s.wait_stream(torch.cuda.current_stream(gpu))
+    with torch.cuda.stream(s):
+        t = base.clone()
+        ev = torch.cuda.Event()
+        ev.record(s)
+    kw = {"wait_event": ev} if wait == "event" else {"wait_stream": s}
+    for n in (0, 1, chunk - 1, chunk, chunk + 1, 2 * chunk + 3):
+        for seed in (0, 0x9E3779B1):
+            assert N.xxh32_of_device(t, n, seed, chunk=chunk, **kw) == N.xxh32_host(buf[:n].tobytes(), seed), (n, seed)
+    s.synchronize()
+
+
 def test_scan_and_gather(gpu):
     rng = np.random.default_rng(0)
     for n in (1, 5, 2047, 2048, 2049, 100000):

@@ -15,7 +15,7 @@
 //      before the first pending match's start (all earlier output is final).
 // Sequences with literals > 12 bytes run one at a time on the whole wave.
 //
-// Measured (tools/probe_coop.py, 262 144 silesia-like blocks, MI355X): the
+// Measured (tools/probe_coop.py (removed; last in `ec1a8c2`), 262 144 silesia-like blocks, MI355X): the
 // decoded prefix is bit-exact and covers 91.6 % of the output (text 99.9 %),
 // at 52 / 80 / 100 GB/s with 16 / 32 / 64 resident waves per CU, against
 // 351 GB/s for the lane decoder: ~44 us per 64-sequence round, i.e. the

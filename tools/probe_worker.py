@@ -1,5 +1,5 @@
 """Dev probe: single-call compress / decompress through the persistent
-workers, with the mailbox state printed (tools/gpu/r04*.sh)."""
+workers, with the mailbox state printed."""
 import ctypes as C
 import os
 import random

@@ -1,5 +1,5 @@
-"""Dev probe (LZ4M_WORKER_TS build, tools/abv_build.sh wts -DLZ4M_WORKER_TS=1):
-where a lone-block call's time goes.  Per case, the mean of the device stages
+"""Dev probe (needs the library built with -DLZ4M_WORKER_TS=1 added to the
+Makefile's FLAGS): where a lone-block call's time goes.  Per case, the mean of the device stages
 (100 MHz real-time clock, from the worker's poll to its done flag) and the
 host's wall time around the C call."""
 import ctypes as C
