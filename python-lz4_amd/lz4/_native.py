@@ -12,9 +12,9 @@ from __future__ import annotations
 import collections
 import ctypes as C
 import os
-import sys
 import threading
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -184,12 +184,19 @@ def _workspace(dev, stream, n: int = 0, src_bytes: int = 0) -> torch.Tensor:
     w = _WORK.pop(key, None)
     if w is None or w.numel() < need:
         w = None
-        with torch.cuda.stream(s):
-            w = torch.empty(need, dtype=torch.uint8, device=dev)
+        w = _empty_on(s, need, dev)
     _WORK[key] = w
     while len(_WORK) > _WORK_STREAMS:
         _WORK.popitem(last=False)
     return w
+
+
+def _empty_on(stream, nbytes: int, dev) -> torch.Tensor:
+    """uint8 scratch allocated on the stream that uses it (None: the current
+    one): when it is dropped the caching allocator hands its memory only to
+    work ordered after that stream's pending launches."""
+    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(dev)):
+        return torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
 
 
 def release_workspaces() -> None:
@@ -223,10 +230,7 @@ def launch_compress(src, src_off, src_len, dst, dst_off, dst_cap, out_len, n, ta
     (lz4m_pcompress_large_batch)."""
     L = lib()
     if table == PARSE_PARALLEL_LARGE and max_len is not None:
-        s = stream if stream is not None else torch.cuda.current_stream(src.device)
-        with torch.cuda.stream(s):   # (allocated on the stream that uses it)
-            work = torch.empty(int(L.lz4m_pcompress_large_workspace_size(n, max_len)), dtype=torch.uint8,
-                               device=src.device)
+        work = _empty_on(stream, L.lz4m_pcompress_large_workspace_size(n, max_len), src.device)
         rc = L.lz4m_pcompress_large_batch(ptr(src), ptr(src_off), ptr(src_len), ptr(dst), ptr(dst_off),
                                           ptr(dst_cap), ptr(out_len), n, max_len, ptr(work), work.numel(),
                                           stream_ptr(stream))
@@ -249,45 +253,23 @@ def launch_compress_dict(src, src_off, src_len, dict_len, dst, dst_off, dst_cap,
 
 
 def launch_compress_hc(src, src_off, src_len, dst, dst_off, dst_cap, out_len, n, level: int = 9, stream=None,
-                       max_len: int = 0) -> None:
+                       max_len: int = 0, dict_len=None) -> None:
     """Batched hash-chain (HC) compression (lz4m_compress_hc_batch): valid
     blocks near the size of LZ4_compress_HC at ``level``, not byte-identical
-    to it.  The chain workspace (256 KiB per block, 320 MiB at most) is
-    allocated per call on the stream that uses it, from torch's caching
-    allocator."""
-    L = lib()
-    if n <= 0:
-        check(L.lz4m_compress_hc_batch(None, None, None, None, None, None, None, n, level, None, 0,
-                                       stream_ptr(stream)), "lz4m_compress_hc_batch")
-        return
-    s = stream if stream is not None else torch.cuda.current_stream(src.device)
-    with torch.cuda.stream(s):
-        work = torch.empty(int(L.lz4m_compress_hc_workspace_size(n, max_len)), dtype=torch.uint8, device=src.device)
-    rc = L.lz4m_compress_hc_batch(ptr(src), ptr(src_off), ptr(src_len), ptr(dst), ptr(dst_off), ptr(dst_cap),
-                                  ptr(out_len), n, level, ptr(work), work.numel(), stream_ptr(stream))
-    check(rc, "lz4m_compress_hc_batch")
-
-
-def launch_compress_hc_dict(src, src_off, src_len, dict_len, dst, dst_off, dst_cap, out_len, n, level: int = 9,
-                            stream=None, max_len: int = 0) -> None:
-    """launch_compress_hc for blocks with history (lz4m_compress_hc_dict_batch):
-    the last min(dict_len[i], 65536) bytes of block i's dictionary precede it
-    in ``src`` (as for launch_compress_dict); dict_len[i] <= 0: no history.
-    The chain workspace (lz4m_compress_hc_dict_workspace_size: 256 KiB per
-    block, 640 MiB at most) is allocated per call on the stream that uses it."""
-    L = lib()
-    if n <= 0:
-        check(L.lz4m_compress_hc_dict_batch(None, None, None, None, None, None, None, None, n, level, None, 0,
-                                            stream_ptr(stream)), "lz4m_compress_hc_dict_batch")
-        return
-    s = stream if stream is not None else torch.cuda.current_stream(src.device)
-    with torch.cuda.stream(s):
-        work = torch.empty(int(L.lz4m_compress_hc_dict_workspace_size(n, max_len)), dtype=torch.uint8,
-                           device=src.device)
-    rc = L.lz4m_compress_hc_dict_batch(ptr(src), ptr(src_off), ptr(src_len), ptr(dict_len), ptr(dst), ptr(dst_off),
-                                       ptr(dst_cap), ptr(out_len), n, level, ptr(work), work.numel(),
-                                       stream_ptr(stream))
-    check(rc, "lz4m_compress_hc_dict_batch")
+    to it.  With ``dict_len`` (int32[n], lz4m_compress_hc_dict_batch) block i
+    has history: the last min(dict_len[i], 65536) bytes of its dictionary
+    precede it in ``src`` (as for launch_compress_dict); dict_len[i] <= 0: no
+    history.  The chain workspace (256 KiB per block; 320 MiB at most, 640
+    with history) is allocated per call on the stream that uses it, from
+    torch's caching allocator."""
+    name = "lz4m_compress_hc_batch" if dict_len is None else "lz4m_compress_hc_dict_batch"
+    size = "lz4m_compress_hc_workspace_size" if dict_len is None else "lz4m_compress_hc_dict_workspace_size"
+    p = ptr if n > 0 else (lambda t: None)   # an empty batch passes no pointers
+    work = _empty_on(stream, getattr(lib(), size)(n, max_len), src.device) if n > 0 else None
+    hist = () if dict_len is None else (p(dict_len),)
+    rc = getattr(lib(), name)(p(src), p(src_off), p(src_len), *hist, p(dst), p(dst_off), p(dst_cap), p(out_len), n,
+                              level, ptr(work), 0 if work is None else work.numel(), stream_ptr(stream))
+    check(rc, name)
 
 
 def launch_compress_linked(src, src_off, src_len, link, dst, dst_off, dst_cap, out_len, n, accel,
@@ -297,7 +279,7 @@ def launch_compress_linked(src, src_off, src_len, link, dst, dst_off, dst_cap, o
     L = lib()
     work = None
     if mode == LINKED_SPECULATIVE:
-        work = torch.empty(int(L.lz4m_compress_linked_workspace_size(n)), dtype=torch.uint8, device=src.device)
+        work = _empty_on(stream, L.lz4m_compress_linked_workspace_size(n), src.device)
     rc = L.lz4m_compress_linked_batch(ptr(src), ptr(src_off), ptr(src_len), ptr(link), ptr(dst), ptr(dst_off),
                                       ptr(dst_cap), ptr(out_len), n, accel, mode, ptr(work),
                                       0 if work is None else work.numel(), stream_ptr(stream))
@@ -351,13 +333,24 @@ def frame_scan(frame, frame_len, pos, block_checksum, content_checksum, max_bloc
 
 
 # ------------------------------------------------------------ host XXH32
-def _addr(buf):
-    """(address, length, keep-alive) of any contiguous buffer, no copy."""
-    import numpy as np
-    if isinstance(buf, torch.Tensor):
-        return buf.data_ptr(), buf.numel() * buf.element_size(), buf
-    a = np.frombuffer(memoryview(buf).cast("B"), dtype=np.uint8)
-    return a.ctypes.data, a.nbytes, a
+_probe = b"lz4m"
+_BYTES_DATA = C.cast(C.c_char_p(_probe), C.c_void_p).value - id(_probe)   # measured, not assumed
+del _probe
+
+
+def host_addr(view: memoryview):
+    """Address of a contiguous host buffer (read-only ones too), None if empty;
+    it holds while the caller keeps ``view``.  A whole bytes object (its data
+    offset measured at import) or a writable buffer takes a fast path; numpy's
+    .ctypes (~2.6 us) serves the rest."""
+    if not view.nbytes:
+        return None
+    obj = view.obj
+    if type(obj) is bytes and view.nbytes == len(obj):
+        return id(obj) + _BYTES_DATA   # CPython: the bytes' data sits at a fixed offset in the object
+    if not view.readonly:
+        return C.addressof(C.c_char.from_buffer(view))
+    return int(np.frombuffer(view, dtype=np.uint8).ctypes.data)
 
 
 class HostXXH32:
@@ -370,9 +363,8 @@ class HostXXH32:
         lib().lz4m_xxh32_host_reset(self._st, seed & 0xFFFFFFFF)
 
     def update(self, buf, n: int | None = None) -> None:
-        ptr, ln, keep = _addr(buf)
-        lib().lz4m_xxh32_host_update(self._st, ptr, ln if n is None else n)
-        del keep
+        mv = memoryview(buf).cast("B")
+        lib().lz4m_xxh32_host_update(self._st, host_addr(mv), mv.nbytes if n is None else n)
 
     def update_ptr(self, ptr: int, n: int) -> None:
         lib().lz4m_xxh32_host_update(self._st, ptr, n)
@@ -383,10 +375,8 @@ class HostXXH32:
 
 def xxh32_host(buf, seed: int = 0) -> int:
     """One-shot XXH32 of a host buffer on the calling host core."""
-    ptr, ln, keep = _addr(buf)
-    r = int(lib().lz4m_xxh32_host(ptr, ln, seed & 0xFFFFFFFF))
-    del keep
-    return r
+    mv = memoryview(buf).cast("B")
+    return int(lib().lz4m_xxh32_host(host_addr(mv), mv.nbytes, seed & 0xFFFFFFFF))
 
 
 _PIN = {}
@@ -444,13 +434,21 @@ def xxh32_of_device_spans(t: torch.Tensor, spans, seed: int = 0, state: "HostXXH
     for lo, hi, ev in spans:
         for a in range(lo, hi, chunk):
             pieces.append((a, min(hi, a + chunk), ev))
-    if not pieces:
-        return st
-    dev = t.device
-    side = torch.cuda.Stream(dev, priority=_HASH_STREAM_PRIORITY)
+    if pieces:
+        side = torch.cuda.Stream(t.device, priority=_HASH_STREAM_PRIORITY)
+        _drain_chunks(t.view(-1), pieces, side, chunk, lambda p, lo, hi: st.update_ptr(p, hi - lo))
+    return st
+
+
+def _drain_chunks(flat: torch.Tensor, pieces, side, chunk: int, consume) -> None:
+    """Device bytes flat[lo:hi] of each piece (lo, hi, event or None), at most
+    ``chunk`` bytes each, to the host in order: copied to two pinned buffers
+    on the stream ``side``, piece i + 1 in flight while ``consume(pinned
+    address, lo, hi)`` takes piece i.  A piece's copy is queued behind its
+    event, each distinct event waited for once.  On an error too, the pinned
+    pair goes back to the pool only once no copy can still write it."""
     bufs = _pinned_pair(chunk)
     evs = [torch.cuda.Event(), torch.cuda.Event()]
-    flat = t.view(-1)
     waited = set()
 
     def issue(i):
@@ -466,14 +464,13 @@ def xxh32_of_device_spans(t: torch.Tensor, spans, seed: int = 0, state: "HostXXH
         issue(0)
         for i, (lo, hi, _ev) in enumerate(pieces):
             if i + 1 < len(pieces):
-                issue(i + 1)   # its buffer was hashed in iteration i - 1
+                issue(i + 1)   # its buffer was consumed in iteration i - 1
             evs[i & 1].synchronize()
-            st.update_ptr(bufs[i & 1].data_ptr(), hi - lo)
+            consume(bufs[i & 1].data_ptr(), lo, hi)
     finally:
         for e in evs:
             e.synchronize()
         _pinned_release(chunk, bufs)
-    return st
 
 
 # ------------------------------------------------------------ host <-> device
@@ -501,7 +498,7 @@ def to_device(buf, dev=None, pad: int = 0) -> torch.Tensor:
     n = mv.nbytes
     out = torch.empty(n + pad, dtype=torch.uint8, device=dev)
     if n >= _BIG:
-        src, _, keep = _addr(mv)
+        src = host_addr(mv)
         bufs = _pinned_pair(_CHUNK)
         evs = [None, None]
         side = torch.cuda.Stream(dev)
@@ -524,7 +521,6 @@ def to_device(buf, dev=None, pad: int = 0) -> torch.Tensor:
                 if e is not None:
                     e.synchronize()
             _pinned_release(_CHUNK, bufs)
-            del keep
     elif n:
         import warnings
         with warnings.catch_warnings():   # read-only bytes: shared, only read
@@ -542,7 +538,6 @@ _PyBytes_New.argtypes = [C.c_void_p, C.c_ssize_t]
 _PyByteArray_New = C.pythonapi.PyByteArray_FromStringAndSize
 _PyByteArray_New.restype = C.py_object
 _PyByteArray_New.argtypes = [C.c_void_p, C.c_ssize_t]
-_BYTES_DATA = sys.getsizeof(b"") - 1   # offset of a bytes object's data (CPython: the header, then the bytes)
 
 
 _MADV_HUGEPAGE = 14
@@ -596,33 +591,14 @@ def to_host_bytes(t: torch.Tensor, n: int, as_bytearray: bool = False, hash_seed
         return (out, xxh32_host(out, hash_seed)) if hash_seed is not None else out
     out, dst = _new_host_buffer(n, as_bytearray)
     st = HostXXH32(hash_seed) if hash_seed is not None else None
-    dev = t.device
-    flat = t.view(-1)
-    side = torch.cuda.Stream(dev)
-    side.wait_stream(torch.cuda.current_stream(dev))
-    bufs = _pinned_pair(_CHUNK)
-    evs = [torch.cuda.Event(), torch.cuda.Event()]
-    spans = [(lo, min(n, lo + _CHUNK)) for lo in range(0, n, _CHUNK)]
-    thr = _copy_threads()
-
-    def issue(i):
-        lo, hi = spans[i]
-        with torch.cuda.stream(side):
-            bufs[i & 1][: hi - lo].copy_(flat[lo:hi], non_blocking=True)
-            evs[i & 1].record(side)
-
-    try:
-        issue(0)
-        for i, (lo, hi) in enumerate(spans):
-            if i + 1 < len(spans):
-                issue(i + 1)   # its buffer was drained in iteration i - 1
-            evs[i & 1].synchronize()
-            lib().lz4m_host_copy(dst + lo, bufs[i & 1].data_ptr(), hi - lo, thr, None if st is None else st._st)
-    finally:
-        for e in evs:
-            e.synchronize()
-        _pinned_release(_CHUNK, bufs)
+    side = torch.cuda.Stream(t.device)
+    side.wait_stream(torch.cuda.current_stream(t.device))
+    chunk, thr = _CHUNK, _copy_threads()
+    hst = None if st is None else st._st   # the copy hashes the chunk as it drains it
+    _drain_chunks(t.view(-1), [(lo, min(n, lo + chunk), None) for lo in range(0, n, chunk)], side, chunk,
+                  lambda p, lo, hi: lib().lz4m_host_copy(dst + lo, p, hi - lo, thr, hst))
     return (out, st.digest()) if st is not None else out
+
 
 def host_copy_many(dsts, srcs, lens) -> None:
     """dsts[i] <- srcs[i], lens[i] bytes each (host addresses), over the copy

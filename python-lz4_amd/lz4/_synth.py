@@ -32,7 +32,7 @@ def _vocab(rng: np.random.Generator, n_words: int, min_len: int = 1, max_len: in
     probs = 1.0 / np.arange(1, _LETTERS.size + 1) ** 0.9
     probs /= probs.sum()
     letters = _LETTERS[rng.choice(_LETTERS.size, size=total, p=probs)]
-    starts = np.concatenate([[0], np.cumsum(lens + 1)[:-1]])
+    starts = np.cumsum(lens + 1) - (lens + 1)
     letters[starts + lens] = ord(" ")
     return letters, starts, lens + 1
 
@@ -73,7 +73,7 @@ def c_source(rng: np.random.Generator, n_bytes: int) -> np.ndarray:
     chunks = [t + b" " for t in toks] + [b"\n    ", b"\n        ", b"\n}\n\n", b"\n"]
     buf = np.frombuffer(b"".join(chunks), dtype=np.uint8).copy()
     lens = np.array([len(c) for c in chunks])
-    starts = np.concatenate([[0], np.cumsum(lens)[:-1]])
+    starts = np.cumsum(lens) - lens
     probs = 1.0 / (np.arange(len(chunks)) + 1.5) ** 0.95
     probs[-4:] = [0.05, 0.03, 0.005, 0.02]
     probs /= probs.sum()

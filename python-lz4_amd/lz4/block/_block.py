@@ -12,7 +12,9 @@ from __future__ import annotations
 
 import ctypes as C
 import operator
+import threading
 
+import numpy as np
 import torch
 
 from .. import _native as N
@@ -82,23 +84,37 @@ def _hc_mode(mode) -> bool:
     raise ValueError(f"Invalid mode argument: {mode}. Must be one of: default, high_compression")
 
 
-_probe = b"lz4m"
-_BYTES_DATA = C.cast(C.c_char_p(_probe), C.c_void_p).value - id(_probe)   # measured, not assumed
-del _probe
+def _cap_and_skip(view: memoryview, uncompressed_size: int):
+    """(output capacity, leading bytes that are not the block) of a
+    decompress source (``_block.c:321-349``): ``uncompressed_size >= 0`` is
+    the capacity and the whole source the block, else a LE32 size header
+    leads it."""
+    if uncompressed_size >= 0:
+        return uncompressed_size, 0
+    if view.nbytes < _HDR:
+        raise ValueError("Input source data size too small")
+    cap = int.from_bytes(view[:4], "little")
+    if cap > INT_MAX:
+        raise ValueError(f"Invalid size: 0x{cap}")
+    return cap, _HDR
 
 
-def _addr(view: memoryview):
-    """Address of a contiguous host buffer (read-only ones too), None if empty.
-    A whole bytes object (its data offset measured at import) or a writable
-    buffer takes a fast path; numpy's .ctypes (~2.6 us) serves the rest."""
-    if not view.nbytes:
-        return None
-    obj = view.obj
-    if type(obj) is bytes and view.nbytes == len(obj):
-        return id(obj) + _BYTES_DATA   # CPython: the bytes' data sits at a fixed offset in the object
-    if not view.readonly:
-        return C.addressof(C.c_char.from_buffer(view))
-    return int(np.frombuffer(view, dtype=np.uint8).ctypes.data)
+def _decode_error(status: int, cap: int, from_header: bool):
+    """The reference's exception for a decoder status (``_block.c:365-380``),
+    None for a good one; a size from the header must be met exactly."""
+    if status < 0:
+        return LZ4BlockError("Decompression failed: corrupt input or insufficient space in destination buffer. "
+                             f"Error code: {-status}")
+    if from_header and status != cap:
+        return LZ4BlockError(f"Decompressor wrote {status} bytes, but {cap} bytes expected from header")
+    return None
+
+
+def _excl_offsets(lens) -> np.ndarray:
+    """int64 start offsets of items of these lengths laid back to back."""
+    out = np.zeros(len(lens), np.int64)
+    np.cumsum(lens[:-1], dtype=np.int64, out=out[1:])
+    return out
 
 
 def _i64(vals, dev) -> torch.Tensor:
@@ -157,7 +173,7 @@ def compress(source, mode="default", store_size=True, acceleration=1, compressio
         hdr = _HDR if store_size else 0
         p = C.c_void_p()
         # the output (after the size header) stays in the thread's pinned buffer: one copy into the result
-        r = N.lib().lz4m_compress_block_api_staged(_addr(src), n, max(N.compress_bound(n), 1), accel, hdr,
+        r = N.lib().lz4m_compress_block_api_staged(N.host_addr(src), n, max(N.compress_bound(n), 1), accel, hdr,
                                                    C.byref(p))
         if r <= 0:
             raise LZ4BlockError("Compression failed")
@@ -166,7 +182,7 @@ def compress(source, mode="default", store_size=True, acceleration=1, compressio
     # dictionary memory that ends where the source begins: the reference's
     # LZ4_compress_fast_continue sees dictEnd == source and takes prefix mode
     # (lz4.c:1671-1676; LZ4_loadDict keeps no dictionary below 8 bytes)
-    prefix = d.nbytes >= 8 and src.nbytes > 0 and _addr(d) + d.nbytes == _addr(src)
+    prefix = d.nbytes >= 8 and src.nbytes > 0 and N.host_addr(d) + d.nbytes == N.host_addr(src)
     out = compress_many([src], accel=accel, store_size=bool(store_size), as_bytearray=bool(return_bytearray),
                         dict=d, dict_prefix=prefix)[0]
     if out is None:
@@ -193,25 +209,14 @@ def decompress(source, uncompressed_size=-1, return_bytearray=False, dict=None):
             raise OverflowError("Dictionary too large for LZ4 API")
     if dview is None or not dview.nbytes:   # one call: lz4m_decompress_safe
         N.require_device()
-        if uncompressed_size >= 0:
-            cap, skip = uncompressed_size, 0
-        else:
-            if src.nbytes < _HDR:
-                raise ValueError("Input source data size too small")
-            cap = int.from_bytes(src[:4], "little")
-            if cap > INT_MAX:
-                raise ValueError(f"Invalid size: 0x{cap}")
-            skip = _HDR
-        sp = _addr(src)
+        cap, skip = _cap_and_skip(src, uncompressed_size)
+        sp = N.host_addr(src)
         p = C.c_void_p()
         # the output stays in the thread's pinned buffer: one copy into the result
         r = N.lib().lz4m_decompress_safe_staged(None if sp is None else sp + skip, src.nbytes - skip, cap, C.byref(p))
-        if r < 0:
-            raise LZ4BlockError(
-                "Decompression failed: corrupt input or insufficient space in destination buffer. "
-                f"Error code: {-r}")
-        if r != cap and uncompressed_size < 0:
-            raise LZ4BlockError(f"Decompressor wrote {r} bytes, but {cap} bytes expected from header")
+        err = _decode_error(r, cap, uncompressed_size < 0)
+        if err is not None:
+            raise err
         out = C.string_at(p.value, r) if r else b""
         return bytearray(out) if return_bytearray else out
     res = decompress_many([src], uncompressed_size=uncompressed_size, dict=dview,
@@ -225,10 +230,6 @@ def decompress(source, uncompressed_size=-1, return_bytearray=False, dict=None):
 # status/lengths + output in ONE device-to-host copy (the reference does one
 # malloc + memcpy per call, _block.c:215, :256-263; a launch per small tensor
 # would dominate a 64 KiB call).
-import threading
-
-import numpy as np
-
 _tls = threading.local()
 _ALIGN = 256
 
@@ -291,7 +292,7 @@ def _stage_in(dev, views, offs, lens, d_off, caps, skip=None):
         dsts, srcs, ns = [], [], []
         for v in views:
             dsts.append(base + pos)
-            srcs.append(_addr(v))
+            srcs.append(N.host_addr(v))
             ns.append(v.nbytes)
             pos += v.nbytes
         N.host_copy_many(dsts, srcs, ns)
@@ -373,31 +374,26 @@ def compress_many(blocks, accel: int = 1, store_size: bool = True, as_bytearray:
         return []
     lens = [v.nbytes for v in views]
     caps = [max(N.compress_bound(L), 1) for L in lens]
-    d_off = np.concatenate([[0], np.cumsum(caps[:-1], dtype=np.int64)]) if n > 1 else np.zeros(1, np.int64)
+    d_off = _excl_offsets(caps)
     if dict is None:
-        offs = np.concatenate([[0], np.cumsum(lens[:-1], dtype=np.int64)]) if n > 1 else np.zeros(1, np.int64)
+        offs = _excl_offsets(lens)
         payload = views
     else:
         dv = _buffer(dict, "dict")
         # LZ4_loadDict keeps the last 64 KiB (lz4.c:1568) and nothing of a dictionary below 8 bytes; HC keeps any
         tail = dv[-65536:] if dv.nbytes >= 8 or hc else dv[:0]
         t = tail.nbytes
-        offs = np.arange(1, n + 1, dtype=np.int64) * t + (np.concatenate([[0], np.cumsum(lens[:-1], dtype=np.int64)])
-                                                            if n > 1 else np.zeros(1, np.int64))
+        offs = np.arange(1, n + 1, dtype=np.int64) * t + _excl_offsets(lens)
         payload = [x for v in views for x in (tail, v)]
     lay, h, d = _stage_in(dev, payload, offs, lens, d_off, caps)
     d_src, src_off, src_len, d_dst, dst_off, dst_cap, out_len = _dev_views(lay, d, n)
-    if hc and dict is not None:
-        dict_len = torch.full((n,), dv.nbytes, dtype=torch.int32, device=dev)
-        N.launch_compress_hc_dict(d_src, src_off, src_len, dict_len, d_dst, dst_off, dst_cap, out_len, n, compression,
-                                  max_len=max(lens))
-    elif hc:
+    dict_len = None if dict is None else torch.full((n,), dv.nbytes, dtype=torch.int32, device=dev)
+    if hc:
         N.launch_compress_hc(d_src, src_off, src_len, d_dst, dst_off, dst_cap, out_len, n, compression,
-                             max_len=max(lens))
+                             max_len=max(lens), dict_len=dict_len)
     elif dict is None:
         N.launch_compress(d_src, src_off, src_len, d_dst, dst_off, dst_cap, out_len, n, table, accel)
     else:
-        dict_len = torch.full((n,), dv.nbytes, dtype=torch.int32, device=dev)
         N.launch_compress_dict(d_src, src_off, src_len, dict_len, d_dst, dst_off, dst_cap, out_len, n, accel,
                                prefix=dict_prefix and dv.nbytes >= 8)
     olen, host = _stage_out(lay, h, d, n)
@@ -434,33 +430,18 @@ def decompress_many(blocks, uncompressed_size=-1, dict=None, as_bytearray: bool 
     sizes = list(uncompressed_size) if isinstance(uncompressed_size, (list, tuple)) else [uncompressed_size] * n
     caps, skip, errors = [], [], [None] * n
     for i, (v, us) in enumerate(zip(views, sizes)):
-        if us >= 0:
-            caps.append(us)
-            skip.append(0)
-        else:
-            if v.nbytes < _HDR:
-                err = ValueError("Input source data size too small")
-                if raise_errors:
-                    raise err
-                errors[i] = err
-                caps.append(0)
-                skip.append(0)
-                continue
-            cap = int.from_bytes(v[:4], "little")
-            if cap > INT_MAX:
-                err = ValueError(f"Invalid size: 0x{cap}")
-                if raise_errors:
-                    raise err
-                errors[i] = err
-                caps.append(0)
-                skip.append(0)
-                continue
-            caps.append(cap)
-            skip.append(_HDR)
+        try:
+            cap, sk = _cap_and_skip(v, us)
+        except ValueError as err:
+            if raise_errors:
+                raise
+            errors[i], cap, sk = err, 0, 0   # decoded as an empty block, reported in its slot
+        caps.append(cap)
+        skip.append(sk)
     dev = N.device()
     lens = [v.nbytes for v in views]
-    offs = np.concatenate([[0], np.cumsum(lens[:-1], dtype=np.int64)]) if n > 1 else np.zeros(1, np.int64)
-    d_off = np.concatenate([[0], np.cumsum(caps[:-1], dtype=np.int64)]) if n > 1 else np.zeros(1, np.int64)
+    offs = _excl_offsets(lens)
+    d_off = _excl_offsets(caps)
     lay, h, d = _stage_in(dev, views, offs, lens, d_off, caps, skip=skip)
     d_src, src_off, src_len, d_dst, dst_off, dst_cap, status = _dev_views(lay, d, n)
     if dict is not None and _buffer(dict).nbytes:
@@ -482,13 +463,7 @@ def decompress_many(blocks, uncompressed_size=-1, dict=None, as_bytearray: bool 
             res.append(errors[i])
             continue
         r = st[i]
-        err = None
-        if r < 0:
-            err = LZ4BlockError(
-                "Decompression failed: corrupt input or insufficient space in destination buffer. "
-                f"Error code: {-r}")
-        elif r != caps[i] and sizes[i] < 0:
-            err = LZ4BlockError(f"Decompressor wrote {r} bytes, but {caps[i]} bytes expected from header")
+        err = _decode_error(r, caps[i], sizes[i] < 0)
         if err is not None:
             if raise_errors:
                 raise err
@@ -543,11 +518,9 @@ def compress_batch(src: torch.Tensor, src_off: torch.Tensor, src_len: torch.Tens
         dst = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
     out_len = torch.empty(n, dtype=torch.int32, device=dev)
     if hc:
-        if n and dict_len is not None:
-            N.launch_compress_hc_dict(src, src_off, src_len, dict_len.to(torch.int32), dst, dst_off, dst_cap, out_len,
-                                      n, compression, stream)
-        elif n:
-            N.launch_compress_hc(src, src_off, src_len, dst, dst_off, dst_cap, out_len, n, compression, stream)
+        if n:
+            N.launch_compress_hc(src, src_off, src_len, dst, dst_off, dst_cap, out_len, n, compression, stream,
+                                 dict_len=None if dict_len is None else dict_len.to(torch.int32))
     else:
         N.launch_compress(src, src_off, src_len, dst, dst_off, dst_cap, out_len, n, int(tab), int(acceleration),
                           stream)

@@ -276,13 +276,11 @@ def _compress_frame(d_src, n=None, *, compression_level=0, block_size=0, content
         cmp = torch.empty(nb * slot, dtype=torch.uint8, device=dev)
         cmp_off = torch.arange(nb, dtype=torch.int64, device=dev) * slot
         cmp_len = torch.empty(nb, dtype=torch.int32, device=dev)
-        if parse == "hc" and linked:
-            # block i's history is the input before it, at most 64 KiB: every block in one launch
-            N.launch_compress_hc_dict(d_src, raw_off, raw_len, raw_off.clamp(max=65536).to(torch.int32), cmp,
-                                      cmp_off, cap, cmp_len, nb, level, stream, max_len=bsize)
-        elif parse == "hc":
+        if parse == "hc":
+            # linked: block i's history is the input before it, at most 64 KiB: every block in one launch
+            hist = raw_off.clamp(max=65536).to(torch.int32) if linked else None
             N.launch_compress_hc(d_src, raw_off, raw_len, cmp, cmp_off, cap, cmp_len, nb, level, stream,
-                                 max_len=bsize)
+                                 max_len=bsize, dict_len=hist)
         elif parse == "exact" and linked:   # one stream across the blocks (lz4frame.c:865-871)
             link = torch.ones(nb, dtype=torch.int32, device=dev)
             link[0] = 0
@@ -385,18 +383,15 @@ def decompress(data, return_bytearray=False, return_bytes_read=False):
         t = lambda v, dt: torch.tensor(v, dtype=dt, device=dev)   # noqa: E731
         args = (d_frame, info, nb, t([r[1] for r in recs], torch.int64), t([r[2] for r in recs], torch.int32),
                 t([r[0] for r in recs], torch.bool), t([r[3] for r in recs], torch.int64))
-        out_t, total, first_err = _decode_records(*args)
+        out_t, total, first_err, _ = _decode_records(*args)
     _frame_errors(first_err, state, info, total)
-    bytes_read = state[1]
     if info["content_checksum"]:   # on the copy the caller gets, hashed while it is staged (lz4frame.c:1850, 1959-1964)
         out, got = N.to_host_bytes(out_t, total, bool(return_bytearray), hash_seed=0)
         if got != struct.unpack_from("<I", mv, state[2])[0]:
             raise _err("LZ4F_decompress", "contentChecksum_invalid")
     else:
         out = N.to_host_bytes(out_t, total, bool(return_bytearray))
-    if return_bytes_read:
-        return out, bytes_read
-    return out
+    return (out, state[1]) if return_bytes_read else out
 
 
 class _FeedHash(threading.Thread):
@@ -472,16 +467,14 @@ def _decompress_pipelined(mv, info, recs, state, as_bytearray):
     c_len = torch.tensor([r[2] for r in recs], dtype=torch.int32, device=dev)
     status = torch.empty(nb, dtype=torch.int32, device=dev)
     sums = torch.empty(nb, dtype=torch.int32, device=dev) if crc else None
-    slots = torch.empty(nb * maxb + 16, dtype=torch.uint8, device=dev)
-    slot_off = torch.arange(nb, dtype=torch.int64, device=dev) * maxb
-    caps = torch.full((nb,), maxb, dtype=torch.int32, device=dev)
+    slots, slot_off, caps = _decode_slots(nb, maxb, dev)
     d_frame = torch.empty(n + 16, dtype=torch.uint8, device=dev)
     d_frame[n:].zero_()
     up.wait_stream(main)   # (after the allocations: their memory may be free only in main's order)
     side.wait_stream(main)
     C = N._CHUNK
     thr = N._copy_threads()
-    src, _, keep = N._addr(mv)
+    src = N.host_addr(mv)
     out, dst = N._new_host_buffer(total, as_bytearray)
     hasher = _FeedHash() if info["content_checksum"] else None
     if hasher is not None:
@@ -566,7 +559,6 @@ def _decompress_pipelined(mv, info, recs, state, as_bytearray):
                 e.synchronize()
         N._pinned_release(C, upb)
         N._pinned_release(C, downb)
-        del keep
     got = hasher.digest() if hasher is not None else None
     main.wait_stream(side)
     if trace is not None:
@@ -578,7 +570,7 @@ def _decompress_pipelined(mv, info, recs, state, as_bytearray):
     ok = (status[: nb - 1] == maxb).all() & (status[nb - 1] == total - (nb - 1) * maxb)
     if crc:
         crc_pos = torch.tensor([r[3] for r in recs], dtype=torch.int64, device=dev)
-        ok = ok & ((sums.to(torch.int64) & 0xFFFFFFFF) == _le32_at(d_frame, crc_pos)).all()
+        ok = ok & ~_crc_mismatch(d_frame, sums, crc_pos).any()
     if not bool(ok):
         return None
     if info["content_checksum"] and got != struct.unpack_from("<I", mv, state[2])[0]:
@@ -606,10 +598,7 @@ def decompress_device(d_frame: torch.Tensor, n: int | None = None, stream=None) 
             raise
         info, hsize = None, 0
     if info is None or info["skippable"] or n <= hsize:
-        # errors and skippable frames: the host path's exact semantics
-        out = decompress(d_frame[:n].cpu().numpy().tobytes())
-        return torch.frombuffer(bytearray(out), dtype=torch.uint8).to(dev) if out else \
-            torch.empty(0, dtype=torch.uint8, device=dev)
+        return _via_host_path(d_frame, n)   # errors and skippable frames
     crc = 4 if info["block_checksum"] else 0
     max_rec = n // 64 + 1024
     rec_pos = torch.empty(max_rec, dtype=torch.int64, device=dev)
@@ -619,19 +608,15 @@ def decompress_device(d_frame: torch.Tensor, n: int | None = None, stream=None) 
     N.frame_scan(d_frame, n, hsize, info["block_checksum"], info["content_checksum"], info["block_size"], max_rec,
                  rec_pos, rec_len, rec_raw, res, stream)
     nb, st, _end, cpos = (int(v) for v in res.cpu().tolist())
-    if st != 0:   # malformed / truncated (or > max_rec records): the host path's exact result or error
-        out = decompress(d_frame[:n].cpu().numpy().tobytes())
-        return torch.frombuffer(bytearray(out), dtype=torch.uint8).to(dev) if out else \
-            torch.empty(0, dtype=torch.uint8, device=dev)
+    if st != 0:   # malformed / truncated (or > max_rec records)
+        return _via_host_path(d_frame, n)
     out_t, total, first_err, got = None, 0, None, None
     if nb:
         crc_pos = rec_pos[:nb] + rec_len[:nb].to(torch.int64) if crc else torch.full((nb,), -1, dtype=torch.int64,
                                                                                       device=dev)
-        follow = bool(info["content_checksum"])
-        r = _decode_records(d_frame, info, nb, rec_pos[:nb], rec_len[:nb], rec_raw[:nb].to(torch.bool), crc_pos,
-                            follow_hash=follow)
-        out_t, total, first_err = r[:3]
-        got = r[3] if follow else None
+        out_t, total, first_err, got = _decode_records(d_frame, info, nb, rec_pos[:nb], rec_len[:nb],
+                                                       rec_raw[:nb].to(torch.bool), crc_pos,
+                                                       follow_hash=bool(info["content_checksum"]))
     _frame_errors(first_err, ("end", _end, cpos if cpos >= 0 else None), info, total)
     if info["content_checksum"]:
         want = int(_le32_at(d_frame, torch.tensor([cpos], dtype=torch.int64, device=dev)).item()) & 0xFFFFFFFF
@@ -642,6 +627,11 @@ def decompress_device(d_frame: torch.Tensor, n: int | None = None, stream=None) 
     if not total:
         return torch.empty(0, dtype=torch.uint8, device=dev)
     return out_t[:total]
+
+
+def _via_host_path(d_frame, n):
+    """decompress_device by ``decompress`` of a host copy of the frame: the host path's exact result or error."""
+    return N.to_device(decompress(d_frame[:n].cpu().numpy().tobytes()), d_frame.device)
 
 
 def _le32_at(d_buf, pos):
@@ -675,13 +665,43 @@ def _frame_errors(first_err, state, info, total):
 _FOLLOW_CHUNKS = 4
 
 
+def _decode_slots(nb, maxb, dev):
+    """(slots, slot_off, caps): a decode slot of the frame's block size per block (lz4frame.c:1844-1847)."""
+    return (torch.empty(nb * maxb + 16, dtype=torch.uint8, device=dev),
+            torch.arange(nb, dtype=torch.int64, device=dev) * maxb,
+            torch.full((nb,), maxb, dtype=torch.int32, device=dev))
+
+
+def _crc_mismatch(d_frame, sums, crc_pos):
+    """Mask of the blocks whose XXH32 (``sums``, int32) is not the LE32 at crc_pos[i] of the frame."""
+    return (sums.to(torch.int64) & 0xFFFFFFFF) != _le32_at(d_frame, crc_pos)
+
+
+def _block_crc_bad(d_frame, info, c_off, c_len, crc_pos):
+    """_crc_mismatch of every block (lz4frame.c:1819: verified first per block); None without block checksums."""
+    if not info["block_checksum"]:
+        return None
+    sums = torch.empty(c_off.numel(), dtype=torch.int32, device=d_frame.device)
+    N.launch_xxh32_batch(d_frame, c_off, c_len.to(torch.int64), 0, sums, c_off.numel())
+    return _crc_mismatch(d_frame, sums, crc_pos)
+
+
+def _first_error(bad_dec, crc_bad):
+    """(index, code) of the first block that failed to decode (mask bad_dec)
+    or whose checksum differs (mask crc_bad or None); None when all are good."""
+    bad = bad_dec if crc_bad is None else (bad_dec | crc_bad)
+    if not bool(bad.any()):
+        return None
+    i = int(torch.nonzero(bad).flatten()[0])
+    return i, "blockChecksum_invalid" if crc_bad is not None and bool(crc_bad[i]) else "decompressionFailed"
+
+
 def _decode_records(d_frame, info, nb, c_off, c_len, raw_mask, crc_pos, follow_hash=False):
     """Decode nb block records of a frame in device memory: payload at
     c_off[i] (int64), stored size c_len[i] (int32), raw_mask[i] = stored
     uncompressed, crc_pos[i] = position of its LE32 block checksum or -1.
-    Returns (out tensor, total decoded bytes, first error or None), and with
-    ``follow_hash`` a fourth item: the content XXH32 of the output, or None
-    when the caller must hash it.
+    Returns (out tensor, total decoded bytes, first error or None, the
+    content XXH32 of the output or None when the caller must hash it).
 
     ``follow_hash`` (independent blocks, no stored ones): the blocks decode
     in _FOLLOW_CHUNKS launches in block order, and a host thread hashes each
@@ -695,41 +715,31 @@ def _decode_records(d_frame, info, nb, c_off, c_len, raw_mask, crc_pos, follow_h
         r = _decode_records_follow(d_frame, info, nb, c_off, c_len, raw_mask, crc_pos)
         if r is not None:
             return r
-        return _decode_records(d_frame, info, nb, c_off, c_len, raw_mask, crc_pos) + (None,)
     dev = d_frame.device
     maxb = info["block_size"]
     status = torch.empty(nb, dtype=torch.int32, device=dev)
-    crc_bad = None
-    if info["block_checksum"]:                                 # lz4frame.c:1819: verified first per block
-        sums = torch.empty(nb, dtype=torch.int32, device=dev)
-        N.launch_xxh32_batch(d_frame, c_off, c_len.to(torch.int64), 0, sums, nb)
-        crc_bad = (sums.to(torch.int64) & 0xFFFFFFFF) != _le32_at(d_frame, crc_pos)
-    slots = torch.empty(nb * maxb + 16, dtype=torch.uint8, device=dev)
-    slot_off = torch.arange(nb, dtype=torch.int64, device=dev) * maxb
+    crc_bad = _block_crc_bad(d_frame, info, c_off, c_len, crc_pos)
+    slots, slot_off, caps = _decode_slots(nb, maxb, dev)
     linked = info["block_linked"] and nb > 1 and not bool(raw_mask.all())
     if linked:
-        _decode_linked(d_frame, c_off, c_len, raw_mask, slots, status, maxb)
+        _decode_linked(d_frame, c_off, c_len, raw_mask, slots, slot_off, caps, status, maxb)
     else:
         # raw blocks are handed to the decoder with length 0 (immediate
         # reject, no work); they are gathered from the frame below
-        caps = torch.full((nb,), maxb, dtype=torch.int32, device=dev)
         dec_len = torch.where(raw_mask, torch.zeros_like(c_len), c_len)
         N.launch_decompress(d_frame, c_off, dec_len, slots, slot_off, caps, status, nb)
     sizes = torch.where(raw_mask, c_len, status) if not linked else status
-    bad_dec = (~raw_mask) & (status < 0)
-    bad = bad_dec if crc_bad is None else (bad_dec | crc_bad)
-    if bool(bad.any()):
-        i = int(torch.nonzero(bad).flatten()[0])
-        code = "blockChecksum_invalid" if crc_bad is not None and bool(crc_bad[i]) else "decompressionFailed"
-        return None, 0, (i, code)
+    err = _first_error((~raw_mask) & (status < 0), crc_bad)
+    if err is not None:
+        return None, 0, err, None
     if linked:
-        return slots, int(sizes.to(torch.int64).sum()), None
+        return slots, int(sizes.to(torch.int64).sum()), None, None
     # no stored block and every block but the last full (what LZ4F_compressFrame
     # writes): the slots already are the output, no gather (one read-back)
     chk = torch.stack([(~raw_mask).all().to(torch.int64), (status[: nb - 1] == maxb).all().to(torch.int64),
                        status[nb - 1].to(torch.int64)]).cpu()
     if int(chk[0]) and int(chk[1]):
-        return slots, (nb - 1) * maxb + int(chk[2]), None
+        return slots, (nb - 1) * maxb + int(chk[2]), None, None
     lens = sizes.to(torch.int32)
     offs = N.exclusive_scan(lens)
     total = int(offs[-1].item())
@@ -740,7 +750,7 @@ def _decode_records(d_frame, info, nb, c_off, c_len, raw_mask, crc_pos, follow_h
         N.gather(slots, slot_off[sel_c], lens[sel_c], out_t, offs[sel_c], sel_c.numel())
     if sel_r.numel():                                          # raw blocks straight from the frame
         N.gather(d_frame, c_off[sel_r], lens[sel_r], out_t, offs[sel_r], sel_r.numel())
-    return out_t, total, None
+    return out_t, total, None, None
 
 
 def _decode_records_follow(d_frame, info, nb, c_off, c_len, raw_mask, crc_pos):
@@ -750,14 +760,8 @@ def _decode_records_follow(d_frame, info, nb, c_off, c_len, raw_mask, crc_pos):
     dev = d_frame.device
     maxb = info["block_size"]
     status = torch.empty(nb, dtype=torch.int32, device=dev)
-    crc_bad = None
-    if info["block_checksum"]:
-        sums = torch.empty(nb, dtype=torch.int32, device=dev)
-        N.launch_xxh32_batch(d_frame, c_off, c_len.to(torch.int64), 0, sums, nb)
-        crc_bad = (sums.to(torch.int64) & 0xFFFFFFFF) != _le32_at(d_frame, crc_pos)
-    slots = torch.empty(nb * maxb + 16, dtype=torch.uint8, device=dev)
-    slot_off = torch.arange(nb, dtype=torch.int64, device=dev) * maxb
-    caps = torch.full((nb,), maxb, dtype=torch.int32, device=dev)
+    crc_bad = _block_crc_bad(d_frame, info, c_off, c_len, crc_pos)
+    slots, slot_off, caps = _decode_slots(nb, maxb, dev)
     bounds = [nb * k // _FOLLOW_CHUNKS for k in range(_FOLLOW_CHUNKS + 1)]
     spans = []
     for k in range(_FOLLOW_CHUNKS):
@@ -775,13 +779,9 @@ def _decode_records_follow(d_frame, info, nb, c_off, c_len, raw_mask, crc_pos):
         # GIL (a tensor read-back waits holding it, and the hash thread needs
         # it between chunks: r05p measured no overlap that way)
         spans[-1][2].synchronize()
-        bad = status < 0
-        if crc_bad is not None:
-            bad = bad | crc_bad
-        if bool(bad.any()):
-            i = int(torch.nonzero(bad).flatten()[0])
-            code = "blockChecksum_invalid" if crc_bad is not None and bool(crc_bad[i]) else "decompressionFailed"
-            return None, 0, (i, code), None
+        err = _first_error(status < 0, crc_bad)
+        if err is not None:
+            return None, 0, err, None
         st = status.cpu()
         full = bool((st[: nb - 1] == maxb).all())
     finally:
@@ -794,7 +794,7 @@ def _decode_records_follow(d_frame, info, nb, c_off, c_len, raw_mask, crc_pos):
     return slots, total, None, state.digest()
 
 
-def _decode_linked(d_frame, c_off, c_len, raw_mask, out, status, maxb):
+def _decode_linked(d_frame, c_off, c_len, raw_mask, out, slot_off, caps, status, maxb):
     """Linked blocks: each block may reference the previous output
     (LZ4F_updateDict, lz4frame.c:1853-1856: LZ4_decompress_safe_usingDict
     with the last <= 64 KiB decoded), contiguously into `out`.
@@ -817,8 +817,6 @@ def _decode_linked(d_frame, c_off, c_len, raw_mask, out, status, maxb):
         return
     dev = d_frame.device
     span = nb * maxb
-    slot_off = torch.arange(nb, dtype=torch.int64, device=dev) * maxb
-    caps = torch.full((nb,), maxb, dtype=torch.int32, device=dev)
     dec_len = torch.where(raw_mask, torch.zeros_like(c_len), c_len)
     dlen = torch.clamp(slot_off, max=65536)
     dict_off = slot_off - dlen

@@ -284,6 +284,35 @@ def test_xxh32_of_device(gpu, wait):
     s.synchronize()
 
 
+_STAGE_BIG, _STAGE_CHUNK = 1 << 16, 1 << 18
+
+
+@pytest.mark.parametrize("n", [_STAGE_BIG, _STAGE_CHUNK - 1, _STAGE_CHUNK, _STAGE_CHUNK + 1, 2 * _STAGE_CHUNK,
+                               3 * _STAGE_CHUNK + 5])
+def test_staged_host_device_copies(gpu, oracle, monkeypatch, n):
+    """The chunked large paths of to_device and to_host_bytes (two pinned
+    chunks), with the thresholds lowered so that a few hundred KiB cover the
+    smallest large size, one chunk less and more than a byte, ends exactly on
+    a chunk edge, and a third chunk that reuses buffer 0: the bytes, the zero
+    pad, the result type and the streamed XXH32 (against the oracle's)."""
+    monkeypatch.setattr(N, "_BIG", _STAGE_BIG)
+    monkeypatch.setattr(N, "_CHUNK", _STAGE_CHUNK)
+    data = np.random.default_rng(n).integers(0, 256, n, dtype=np.uint8).tobytes()
+    want = {seed: oracle.xxh32(data, seed) for seed in (0, 0x9E3779B1)}
+    for pad in (0, 16):
+        d = N.to_device(data, gpu, pad=pad)
+        assert d.dtype == torch.uint8 and d.numel() == n + pad
+        assert not bool(d[n:].any()), pad
+        for as_bytearray in (False, True):
+            for seed in (None, 0, 0x9E3779B1):
+                r = N.to_host_bytes(d, n, as_bytearray, hash_seed=seed)
+                out, digest = r if seed is not None else (r, None)
+                assert type(out) is (bytearray if as_bytearray else bytes), (pad, as_bytearray, seed)
+                assert out == data, (pad, as_bytearray, seed)
+                if seed is not None:
+                    assert digest == want[seed], (pad, as_bytearray, seed)
+
+
 def test_scan_and_gather(gpu):
     rng = np.random.default_rng(0)
     for n in (1, 5, 2047, 2048, 2049, 100000):
