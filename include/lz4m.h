@@ -510,6 +510,141 @@ int lz4m_frame_scan(const uint8_t* d_frame, int64_t frame_len, int64_t pos, int 
                     int content_checksum, int32_t max_block, int64_t max_rec, int64_t* d_rec_pos,
                     int32_t* d_rec_len, uint8_t* d_rec_raw, int64_t* d_result, lz4m_stream_t stream);
 
+/*
+ * Batched frames (lz4m_frames.hip): n complete LZ4 frames in one device
+ * buffer, the per-frame steps on one lane per frame, the frames side by side.
+ * Every call below is stream-ordered, allocates nothing and does not
+ * synchronise; n is at most 2^31 - 1 frames.
+ *
+ * Per-frame status of lz4m_frames_scan.  A frame with a non-zero status other
+ * than LZ4M_FRAME_SKIPPABLE is malformed; the codes follow the order in which
+ * LZ4F_decodeHeader (lz4frame.c:1291-1380) and the block-header states of
+ * LZ4F_decompress (lz4frame.c:1643-1701, 1926-1965) reject a frame.
+ */
+#define LZ4M_FRAME_OK                        0
+#define LZ4M_FRAME_HEADER_INCOMPLETE         1   /* fewer bytes than the header needs (lz4frame.c:1299) */
+#define LZ4M_FRAME_MAGIC_UNKNOWN             2   /* lz4frame.c:1319 */
+#define LZ4M_FRAME_RESERVED_FLAG             3   /* FLG bit 1, BD bit 7 or BD bits 0-3 (lz4frame.c:1333, 1353, 1355) */
+#define LZ4M_FRAME_VERSION_WRONG             4   /* lz4frame.c:1334 */
+#define LZ4M_FRAME_BLOCK_SIZE_ID             5   /* block-size id below 4 (lz4frame.c:1354) */
+#define LZ4M_FRAME_HEADER_CHECKSUM           6   /* lz4frame.c:1359-1362 */
+#define LZ4M_FRAME_BLOCK_TOO_LARGE           7   /* a record's size above the frame's block size (lz4frame.c:1681) */
+#define LZ4M_FRAME_TRUNCATED                 8   /* the bytes end inside a record, before the endmark, or inside a
+                                                    skippable frame */
+#define LZ4M_FRAME_CONTENT_CHECKSUM_MISSING  9   /* the bytes end before the 4 bytes after the endmark */
+#define LZ4M_FRAME_SKIPPABLE                10   /* a complete skippable frame (lz4frame.c:1303-1311): no content */
+/* what lz4.frame.decompress_batch adds after decoding (not set by the scan) */
+#define LZ4M_FRAME_BLOCK_FAILED             16   /* a block did not decode (lz4frame.c:1848) */
+#define LZ4M_FRAME_BLOCK_CHECKSUM_BAD       17   /* lz4frame.c:1821 */
+#define LZ4M_FRAME_CONTENT_SIZE_WRONG       18   /* lz4frame.c:1927 */
+#define LZ4M_FRAME_CONTENT_CHECKSUM_BAD     19   /* lz4frame.c:1963 */
+/* bits of d_flags[i] */
+#define LZ4M_FRAME_LINKED            1   /* blocks are linked (FLG bit 5 clear) */
+#define LZ4M_FRAME_BLOCK_CHECKSUM    2
+#define LZ4M_FRAME_CONTENT_CHECKSUM  4
+#define LZ4M_FRAME_CONTENT_SIZE      8   /* the header stores the content size */
+#define LZ4M_FRAME_DICT_ID          16   /* the header has a dictionary id (skipped, as LZ4F_decompress does
+                                            without a dictionary) */
+
+/*
+ * First pass of a batched frame decode.  Frame i is the d_frame_len[i] bytes
+ * at d_buf + d_frame_off[i]; bytes after the frame's end are allowed.  One
+ * lane per frame parses the header (LZ4F_headerSize + LZ4F_decodeHeader,
+ * lz4frame.c:1291-1380, 1387-1463: magic, skippable magic, FLG / BD reserved
+ * bits, version, block-size id, optional content size and dictionary id, and
+ * the header checksum byte (XXH32(descriptor) >> 8) & 0xFF, lz4frame.c:1359,
+ * computed in the kernel), then walks the block records as lz4m_frame_scan
+ * does (lz4frame.c:1643-1701, 1926-1965) and counts them.
+ * Outputs, one entry per frame: d_status (LZ4M_FRAME_*), d_nblocks (0 unless
+ * the status is LZ4M_FRAME_OK), d_hsize (header bytes; 8 for a skippable
+ * frame), d_end (bytes consumed, counted from the frame's start; 0 for a
+ * malformed frame), d_cpos (position IN d_buf of the LE32 content checksum,
+ * or -1), d_bsid (block-size id 4..7), d_flags (LZ4M_FRAME_* bits) and
+ * d_content_size (the stored size, 0 when absent).  Frames are independent:
+ * a malformed frame only sets its own status.
+ */
+int lz4m_frames_scan(const uint8_t* d_buf, const int64_t* d_frame_off, const int64_t* d_frame_len, int64_t n,
+                     int32_t* d_status, int32_t* d_nblocks, int32_t* d_hsize, int64_t* d_end, int64_t* d_cpos,
+                     int32_t* d_bsid, int32_t* d_flags, int64_t* d_content_size, lz4m_stream_t stream);
+
+/*
+ * Second pass, after an exclusive scan of d_nblocks into d_block_base
+ * (lz4m_exclusive_scan; n + 1 entries): one lane per frame walks its records
+ * again (one dependent read per record; the frames run in parallel) and fills
+ * the global per-block arrays at d_block_base[i] + k: d_rec_pos (payload
+ * position in d_buf), d_rec_len (stored size), d_rec_raw (stored
+ * uncompressed, bit 31 of the record header), d_rec_crc (position in d_buf of
+ * the LE32 block checksum, or -1), d_rec_frame (the owning frame i),
+ * d_slot_off = d_slot_base[i] + k * block size and d_slot_cap = the frame's
+ * block size: the block's output slot (the capacity LZ4F_decompress gives,
+ * lz4frame.c:1844-1847).  The other arguments are lz4m_frames_scan's outputs.
+ */
+int lz4m_frames_records(const uint8_t* d_buf, const int64_t* d_frame_off, const int64_t* d_frame_len,
+                        const int32_t* d_nblocks, const int32_t* d_hsize, const int32_t* d_bsid,
+                        const int32_t* d_flags, const int64_t* d_block_base, const int64_t* d_slot_base, int64_t n,
+                        int64_t* d_rec_pos, int32_t* d_rec_len, uint8_t* d_rec_raw, int64_t* d_rec_crc,
+                        int64_t* d_rec_frame, int64_t* d_slot_off, int32_t* d_slot_cap, lz4m_stream_t stream);
+
+/*
+ * lz4m_decompress_chain for a batch: n_chains linked-block chains, one
+ * wavefront (one workgroup) each, side by side.  Chain c decodes blocks
+ * [d_first[c], d_first[c] + d_count[c]) of the block arrays d_src_off /
+ * d_src_len / d_raw_flag / d_status in order, contiguously from
+ * d_dst + d_dst_off[c], with capacity d_max_block[c] per block; its history
+ * is its own output, up to 64 KiB (lz4frame.c:1853-1856).  A chain needs
+ * d_count[c] * d_max_block[c] bytes at its offset; d_count[c] <= 0 does
+ * nothing.  Statuses as lz4m_decompress_chain: after a chain's first failing
+ * block its remaining statuses are -1; other chains are untouched.
+ */
+int lz4m_decompress_chains(const uint8_t* d_src, const int64_t* d_src_off, const int32_t* d_src_len,
+                           const uint8_t* d_raw_flag, const int64_t* d_first, const int32_t* d_count,
+                           uint8_t* d_dst, const int64_t* d_dst_off, const int32_t* d_max_block, int32_t* d_status,
+                           int64_t n_chains, lz4m_stream_t stream);
+
+/*
+ * Block plan of a batched frame compression.  lz4m_frames_plan, one lane per
+ * frame of d_src_len[i] bytes: d_bsid = the block-size id LZ4F_compressFrame
+ * uses (LZ4F_optimalBSID of block_size_id, lz4frame.c:351-363; 0 = the
+ * default, 64 KiB; -1 when that is no block size, the caller's
+ * ERROR_maxBlockSize_invalid), d_nblocks = its block count, d_linked =
+ * block_linked && length > block size (lz4frame.c:441-442).
+ * lz4m_frames_plan_blocks, after an exclusive scan of d_nblocks into
+ * d_block_base (n + 1 entries, n_blocks = its last), one lane per block:
+ * d_raw_off (position in the source buffer, d_src_off[i] + k * block size),
+ * d_raw_len, d_cap = d_raw_len - 1 (lz4frame.c:835), d_link (0 on a frame's
+ * first block and in unlinked frames: lz4m_compress_linked_batch's flag),
+ * d_hist = min(offset within the frame, 65536) in linked frames, else 0
+ * (lz4m_compress_hc_dict_batch's d_dict_len), d_owner (the frame) and
+ * d_slot_len = LZ4_compressBound(d_raw_len).
+ */
+int lz4m_frames_plan(const int64_t* d_src_len, int64_t n, int32_t block_size_id, int32_t block_linked,
+                     int32_t* d_bsid, int32_t* d_nblocks, int32_t* d_linked, lz4m_stream_t stream);
+int lz4m_frames_plan_blocks(const int64_t* d_src_off, const int64_t* d_src_len, const int32_t* d_bsid,
+                            const int32_t* d_linked, const int64_t* d_block_base, int64_t n, int64_t n_blocks,
+                            int64_t* d_raw_off, int32_t* d_raw_len, int32_t* d_cap, int32_t* d_link,
+                            int32_t* d_hist, int64_t* d_owner, int32_t* d_slot_len, lz4m_stream_t stream);
+
+/*
+ * Frame assembly.  lz4m_frames_sizes: from d_rec_off, the exclusive scan of
+ * the per-block record sizes (lz4m_frame_block_sizes; n_blocks + 1 entries),
+ * d_hsize[i] = 7, or 15 with a stored content size (store_size and a
+ * non-empty input, lz4frame.c:757-762), and d_frame_size[i] = header +
+ * records + endmark (+ 4 with content_checksum); the frame offsets are one
+ * scan of these.  lz4m_frames_emit then writes at d_frames + d_frame_off[i]
+ * the header (magic, FLG, BD, content size, header checksum byte computed on
+ * the device; lz4frame.c:752-780), after the last record the 4-byte endmark
+ * (lz4frame.c:1167) and, with content_checksum, the LE32 of d_content_hash[i]
+ * (lz4frame.c:1170-1176).  The records between them are lz4m_frame_emit's,
+ * at d_frame_off[i] + d_hsize[i] + (d_rec_off[b] - d_rec_off[first block]).
+ */
+int lz4m_frames_sizes(const int64_t* d_rec_off, const int64_t* d_block_base, const int64_t* d_src_len,
+                      int store_size, int content_checksum, int64_t n, int32_t* d_hsize, int64_t* d_frame_size,
+                      lz4m_stream_t stream);
+int lz4m_frames_emit(uint8_t* d_frames, const int64_t* d_frame_off, const int64_t* d_frame_size,
+                     const int32_t* d_bsid, const int32_t* d_linked, const int64_t* d_src_len, int store_size,
+                     int block_checksum, int content_checksum, const uint32_t* d_content_hash, int64_t n,
+                     lz4m_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

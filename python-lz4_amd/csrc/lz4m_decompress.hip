@@ -1120,13 +1120,11 @@ __global__ __launch_bounds__(256) void decompress_worker(Mailbox* mb, uint8_t* h
 // copies.  Prefix semantics = LZ4_decompress_safe_usingDict with the
 // previous output as a contiguous prefix (withSmallPrefix / withPrefix64k,
 // lz4.c:2612-2625): offsets may reach min(prefix, 64 KiB) before the block.
-__global__ __launch_bounds__(64) void decompress_chain_kernel(const uint8_t* __restrict__ src,
-                                                              const int64_t* __restrict__ src_off,
-                                                              const int32_t* __restrict__ src_len,
-                                                              const uint8_t* __restrict__ raw_flag, uint8_t* dst,
-                                                              int32_t* __restrict__ status, int64_t n,
-                                                              int32_t max_block) {
-    const uint32_t lane = threadIdx.x;
+__device__ __forceinline__ void chain_decode(const uint8_t* __restrict__ src, const int64_t* __restrict__ src_off,
+                                             const int32_t* __restrict__ src_len,
+                                             const uint8_t* __restrict__ raw_flag, uint8_t* dst,
+                                             int32_t* __restrict__ status, int64_t n, int32_t max_block,
+                                             uint32_t lane) {
     int64_t running = 0;
     for (int64_t b = 0; b < n; ++b) {
         const int64_t len = src_len[b];
@@ -1191,6 +1189,36 @@ __global__ __launch_bounds__(64) void decompress_chain_kernel(const uint8_t* __r
         }
         running += r;
     }
+}
+
+__global__ __launch_bounds__(64) void decompress_chain_kernel(const uint8_t* __restrict__ src,
+                                                              const int64_t* __restrict__ src_off,
+                                                              const int32_t* __restrict__ src_len,
+                                                              const uint8_t* __restrict__ raw_flag, uint8_t* dst,
+                                                              int32_t* __restrict__ status, int64_t n,
+                                                              int32_t max_block) {
+    chain_decode(src, src_off, src_len, raw_flag, dst, status, n, max_block, threadIdx.x);
+}
+
+// The same chain for a batch of frames: one workgroup of one wavefront per
+// chain, chain c over blocks [first[c], first[c] + count[c]) of the block
+// arrays, contiguously from dst + dst_off[c].  A chain is serial (block k
+// reads block k-1's output); the chains run side by side.
+__global__ __launch_bounds__(64) void decompress_chains_kernel(const uint8_t* __restrict__ src,
+                                                               const int64_t* __restrict__ src_off,
+                                                               const int32_t* __restrict__ src_len,
+                                                               const uint8_t* __restrict__ raw_flag,
+                                                               const int64_t* __restrict__ first,
+                                                               const int32_t* __restrict__ count, uint8_t* dst,
+                                                               const int64_t* __restrict__ dst_off,
+                                                               const int32_t* __restrict__ max_block,
+                                                               int32_t* __restrict__ status) {
+    const int64_t c = blockIdx.x;
+    const int64_t n = count[c];
+    if (n <= 0) return;
+    const int64_t f = first[c];
+    chain_decode(src, src_off + f, src_len + f, raw_flag + f, dst + dst_off[c], status + f, n, max_block[c],
+                 threadIdx.x);
 }
 
 }  // namespace lz4m
@@ -1348,3 +1376,15 @@ extern "C" int lz4m_decompress_chain(const uint8_t* d_src, const int64_t* d_src_
     return (int)hipGetLastError();
 }
 
+
+extern "C" int lz4m_decompress_chains(const uint8_t* d_src, const int64_t* d_src_off, const int32_t* d_src_len,
+                                      const uint8_t* d_raw_flag, const int64_t* d_first, const int32_t* d_count,
+                                      uint8_t* d_dst, const int64_t* d_dst_off, const int32_t* d_max_block,
+                                      int32_t* d_status, int64_t n_chains, lz4m_stream_t stream) {
+    if (n_chains < 0 || n_chains > 0x7FFFFFFF) return LZ4M_EINVAL;
+    if (n_chains == 0) return 0;
+    if (!d_first || !d_count || !d_dst_off || !d_max_block || !d_status) return LZ4M_EINVAL;
+    hipLaunchKernelGGL(decompress_chains_kernel, dim3((uint32_t)n_chains), dim3(64), 0, (hipStream_t)stream, d_src,
+                       d_src_off, d_src_len, d_raw_flag, d_first, d_count, d_dst, d_dst_off, d_max_block, d_status);
+    return (int)hipGetLastError();
+}

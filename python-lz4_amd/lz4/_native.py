@@ -71,6 +71,13 @@ def _declare(lib) -> None:
         "lz4m_frame_block_sizes": ([vp, vp, i32, vp, i64, vp], i32),
         "lz4m_frame_emit": ([vp, vp, vp, vp, vp, vp, vp, vp, i32, i64, vp], i32),
         "lz4m_frame_scan": ([vp, i64, i64, i32, i32, i32, i64, vp, vp, vp, vp, vp], i32),
+        "lz4m_frames_scan": ([vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp], i32),
+        "lz4m_frames_records": ([vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp], i32),
+        "lz4m_decompress_chains": ([vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp], i32),
+        "lz4m_frames_plan": ([vp, i64, i32, i32, vp, vp, vp, vp], i32),
+        "lz4m_frames_plan_blocks": ([vp, vp, vp, vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp], i32),
+        "lz4m_frames_sizes": ([vp, vp, vp, i32, i32, i64, vp, vp, vp], i32),
+        "lz4m_frames_emit": ([vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, i64, vp], i32),
         "lz4m_decompress_safe": ([vp, vp, i32, i32], i32),
         "lz4m_compress_default": ([vp, vp, i32, i32], i32),
         "lz4m_compress_block_api": ([vp, vp, i32, i32, i32], i32),
@@ -330,6 +337,89 @@ def frame_scan(frame, frame_len, pos, block_checksum, content_checksum, max_bloc
                                max_block, max_rec, ptr(rec_pos), ptr(rec_len), ptr(rec_raw), ptr(result),
                                stream_ptr(stream))
     check(rc, "lz4m_frame_scan")
+
+
+# status codes and flag bits of the batched frame calls (include/lz4m.h LZ4M_FRAME_*)
+FRAME_OK, FRAME_SKIPPABLE = 0, 10
+FRAME_BLOCK_FAILED, FRAME_BLOCK_CHECKSUM_BAD, FRAME_CONTENT_SIZE_WRONG, FRAME_CONTENT_CHECKSUM_BAD = 16, 17, 18, 19
+FRAME_LINKED, FRAME_BLOCK_CHECKSUM, FRAME_CONTENT_CHECKSUM = 1, 2, 4
+
+
+def frames_scan(buf, frame_off, frame_len, n, stream=None) -> dict:
+    """lz4m_frames_scan over n frames: a dict of its per-frame output tensors."""
+    dev = buf.device
+    i32 = lambda: torch.empty(n, dtype=torch.int32, device=dev)   # noqa: E731
+    i64 = lambda: torch.empty(n, dtype=torch.int64, device=dev)   # noqa: E731
+    r = {"status": i32(), "nblocks": i32(), "hsize": i32(), "end": i64(), "cpos": i64(), "bsid": i32(),
+         "flags": i32(), "content_size": i64()}
+    rc = lib().lz4m_frames_scan(ptr(buf), ptr(frame_off), ptr(frame_len), n, ptr(r["status"]), ptr(r["nblocks"]),
+                                ptr(r["hsize"]), ptr(r["end"]), ptr(r["cpos"]), ptr(r["bsid"]), ptr(r["flags"]),
+                                ptr(r["content_size"]), stream_ptr(stream))
+    check(rc, "lz4m_frames_scan")
+    return r
+
+
+def frames_records(buf, frame_off, frame_len, scan: dict, block_base, slot_base, n, n_blocks, stream=None) -> dict:
+    """lz4m_frames_records: a dict of the per-block arrays (n_blocks entries each)."""
+    dev = buf.device
+    t = lambda dt: torch.empty(n_blocks, dtype=dt, device=dev)   # noqa: E731
+    r = {"pos": t(torch.int64), "len": t(torch.int32), "raw": t(torch.uint8), "crc": t(torch.int64),
+         "frame": t(torch.int64), "slot_off": t(torch.int64), "slot_cap": t(torch.int32)}
+    rc = lib().lz4m_frames_records(ptr(buf), ptr(frame_off), ptr(frame_len), ptr(scan["nblocks"]),
+                                   ptr(scan["hsize"]), ptr(scan["bsid"]), ptr(scan["flags"]), ptr(block_base),
+                                   ptr(slot_base), n, ptr(r["pos"]), ptr(r["len"]), ptr(r["raw"]), ptr(r["crc"]),
+                                   ptr(r["frame"]), ptr(r["slot_off"]), ptr(r["slot_cap"]), stream_ptr(stream))
+    check(rc, "lz4m_frames_records")
+    return r
+
+
+def launch_decompress_chains(src, src_off, src_len, raw_flag, first, count, dst, dst_off, max_block, status,
+                             n_chains, stream=None) -> None:
+    rc = lib().lz4m_decompress_chains(ptr(src), ptr(src_off), ptr(src_len), ptr(raw_flag), ptr(first), ptr(count),
+                                      ptr(dst), ptr(dst_off), ptr(max_block), ptr(status), n_chains,
+                                      stream_ptr(stream))
+    check(rc, "lz4m_decompress_chains")
+
+
+def frames_plan(src_len, n, block_size_id: int, block_linked: bool, stream=None):
+    """lz4m_frames_plan: (bsid, nblocks, linked), int32 per frame."""
+    dev = src_len.device
+    out = [torch.empty(n, dtype=torch.int32, device=dev) for _ in range(3)]
+    rc = lib().lz4m_frames_plan(ptr(src_len), n, block_size_id, int(bool(block_linked)), ptr(out[0]), ptr(out[1]),
+                                ptr(out[2]), stream_ptr(stream))
+    check(rc, "lz4m_frames_plan")
+    return out
+
+
+def frames_plan_blocks(src_off, src_len, bsid, linked, block_base, n, n_blocks, stream=None) -> dict:
+    """lz4m_frames_plan_blocks: a dict of the per-block arrays."""
+    dev = src_len.device
+    t = lambda dt: torch.empty(n_blocks, dtype=dt, device=dev)   # noqa: E731
+    r = {"raw_off": t(torch.int64), "raw_len": t(torch.int32), "cap": t(torch.int32), "link": t(torch.int32),
+         "hist": t(torch.int32), "owner": t(torch.int64), "slot_len": t(torch.int32)}
+    rc = lib().lz4m_frames_plan_blocks(ptr(src_off), ptr(src_len), ptr(bsid), ptr(linked), ptr(block_base), n,
+                                       n_blocks, ptr(r["raw_off"]), ptr(r["raw_len"]), ptr(r["cap"]), ptr(r["link"]),
+                                       ptr(r["hist"]), ptr(r["owner"]), ptr(r["slot_len"]), stream_ptr(stream))
+    check(rc, "lz4m_frames_plan_blocks")
+    return r
+
+
+def frames_sizes(rec_off, block_base, src_len, store_size, content_checksum, n, stream=None):
+    """lz4m_frames_sizes: (hsize int32, frame_size int64) per frame."""
+    hsize = torch.empty(n, dtype=torch.int32, device=src_len.device)
+    size = torch.empty(n, dtype=torch.int64, device=src_len.device)
+    rc = lib().lz4m_frames_sizes(ptr(rec_off), ptr(block_base), ptr(src_len), int(bool(store_size)),
+                                 int(bool(content_checksum)), n, ptr(hsize), ptr(size), stream_ptr(stream))
+    check(rc, "lz4m_frames_sizes")
+    return hsize, size
+
+
+def frames_emit(frames, frame_off, frame_size, bsid, linked, src_len, store_size, block_checksum, content_checksum,
+                content_hash, n, stream=None) -> None:
+    rc = lib().lz4m_frames_emit(ptr(frames), ptr(frame_off), ptr(frame_size), ptr(bsid), ptr(linked), ptr(src_len),
+                                int(bool(store_size)), int(bool(block_checksum)), int(bool(content_checksum)),
+                                ptr(content_hash), n, stream_ptr(stream))
+    check(rc, "lz4m_frames_emit")
 
 
 # ------------------------------------------------------------ host XXH32

@@ -7,8 +7,12 @@ LZ4FrameFile, ...) is outside this codec's scope.
 from ._frame import (  # noqa: F401
     compress,
     compress_device,
+    compress_batch,
+    compress_many,
     decompress_device,
     decompress,
+    decompress_batch,
+    decompress_many,
     get_frame_info,
     BLOCKSIZE_DEFAULT,
     BLOCKSIZE_MAX64KB,

@@ -23,6 +23,13 @@ LE32 block records); every byte-level operation runs on the GPU:
   verified on the device, the content checksum on a host core.  Linked-block frames decode
   block after block on one wavefront with the previous output as prefix.
 
+* many frames per call (compress_batch / decompress_batch on device tensors,
+  compress_many / decompress_many on lists of host buffers; at the end of
+  this module): the per-frame steps above run on the
+  device, one lane per frame, the blocks of all frames in the same batched
+  launches, linked frames one wavefront each, content checksums on the
+  device.
+
 Scope notes: every frame ``compress`` writes is byte-identical
 to the reference's (``parse="parallel"`` on ``compress_device`` trades that
 for speed); HC levels (>= 3) and the chunked / context streaming API are
@@ -225,14 +232,8 @@ def _host_wait(stream) -> None:
     ev.synchronize()
 
 
-def _compress_frame(d_src, n=None, *, compression_level=0, block_size=0, content_checksum=False,
-                    block_checksum=False, block_linked=True, store_size=True, parse="exact", stream=None,
-                    host_src=None):
-    """compress_device, also returning the block records:
-    (frame, {"data_off", "stored_len", "raw"}) with device tensors giving, per
-    block, the payload position in the frame, its stored length and whether
-    it is stored raw (None when the input is empty)."""
-    n = d_src.numel() if n is None else int(n)
+def _parse_level(parse, compression_level):
+    """(level, acceleration) of a device compression call, or its argument error."""
     level = int(compression_level)
     if parse not in ("exact", "parallel", "hc"):
         raise ValueError("parse must be 'exact', 'parallel' or 'hc'")
@@ -241,7 +242,18 @@ def _compress_frame(d_src, n=None, *, compression_level=0, block_size=0, content
             raise ValueError("parse='hc' needs compression_level >= 3 (levels 0-2 are the fast compressor)")
     elif level >= 3:
         raise NotImplementedError("LZ4 HC compression levels (>= 3) are outside the MI355X codec's scope")
-    accel = -level + 1 if level < 0 else 1                     # lz4frame.c:855
+    return level, (-level + 1 if level < 0 else 1)             # lz4frame.c:855
+
+
+def _compress_frame(d_src, n=None, *, compression_level=0, block_size=0, content_checksum=False,
+                    block_checksum=False, block_linked=True, store_size=True, parse="exact", stream=None,
+                    host_src=None):
+    """compress_device, also returning the block records:
+    (frame, {"data_off", "stored_len", "raw"}) with device tensors giving, per
+    block, the payload position in the frame, its stored length and whether
+    it is stored raw (None when the input is empty)."""
+    n = d_src.numel() if n is None else int(n)
+    level, accel = _parse_level(parse, compression_level)
     bsid = _optimal_bsid(int(block_size), n)
     if bsid == 0:
         bsid = BLOCKSIZE_MAX64KB                               # LZ4F_BLOCKSIZEID_DEFAULT
@@ -859,3 +871,317 @@ def _linked_status(d_frame, c_off, c_len, raw_mask, out, status, nb, maxb, st):
         N.launch_decompress_chain(d_frame, c_off, c_len, raw_mask, out, status, nb, maxb)
         return
     status.copy_(st)
+
+
+# ------------------------------------------------------------ batched frames
+# Many frames per call.  What is serial inside a frame
+# (its header, the walk over its block records, a linked chain, its content
+# hash) runs on one lane or one wavefront per frame, the frames side by side;
+# the blocks of all frames share the block-batched launches.  The number of
+# launches and host synchronisations of a call does not depend on the number
+# of frames: the host reads back totals (block count, buffer sizes) only.
+# Linked frames with at least this many blocks on average, in a batch of few
+# linked frames, compress speculatively (a wavefront per block); otherwise one
+# wavefront per frame, which is parallel over the frames
+_BATCH_SPEC_MAX_FRAMES = 256
+
+
+def _on(stream):
+    import contextlib
+    return torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
+
+
+def _spans(buf, off, length, what):
+    """(int64 offsets, int64 lengths, sum of the lengths) of n spans of a uint8 device tensor, checked to lie
+    inside it (one read-back)."""
+    if buf.dtype != torch.uint8 or not buf.is_cuda:
+        raise TypeError(f"{what} must be a uint8 device tensor")
+    if off.numel() != length.numel():
+        raise ValueError(f"{what}: offsets and lengths differ in count")
+    off = off.to(device=buf.device, dtype=torch.int64).contiguous().view(-1)
+    length = length.to(device=buf.device, dtype=torch.int64).contiguous().view(-1)
+    if off.numel() == 0:
+        return off, length, 0
+    lo, neg, hi, total = torch.stack([off.min(), length.min(), (off + length).max(), length.sum()]).tolist()
+    if lo < 0 or neg < 0 or hi > buf.numel():
+        raise ValueError(f"{what}: a span reaches outside the buffer")
+    return off, length, total
+
+
+def _launch_subset(mask, arrays, out_len, launch):
+    """launch(*arrays restricted to the blocks of `mask`, out, count); the blocks' results go to out_len."""
+    nb = mask.numel()
+    sel = torch.nonzero(mask).flatten()
+    m = sel.numel()
+    if m == 0:
+        return
+    if m == nb:
+        launch(*arrays, out_len, nb)
+        return
+    out = torch.empty(m, dtype=torch.int32, device=mask.device)
+    launch(*(a[sel] for a in arrays), out, m)
+    out_len[sel] = out
+
+
+def compress_batch(src, src_off, src_len, *, compression_level=0, block_size=0, content_checksum=False,
+                   block_checksum=False, block_linked=True, store_size=True, parse="exact", stream=None):
+    """compress_device for n inputs in one call: input i is
+    src[src_off[i] : src_off[i] + src_len[i]] of a uint8 device tensor.
+    Returns (frames, frame_off, frame_len): frame i is
+    frames[frame_off[i] : frame_off[i] + frame_len[i]] (int64 device tensors;
+    the frames lie back to back).  Frame i holds the bytes of
+    ``compress_device(input i, same options)`` for parse="exact" and
+    parse="hc"; parse="parallel" gives valid frames of the parallel parse.
+
+    The blocks of all frames are compressed together: those of linked frames
+    (block_linked and an input above one block) as one stream per frame
+    (lz4m_compress_linked_batch; parse="hc": lz4m_compress_hc_dict_batch with
+    each block's history), all others as independent blocks -- a batch whose
+    inputs straddle the block size uses both.  Content checksums are hashed
+    on the device, four lanes per frame (lz4m_xxh32_batch): a very large frame
+    in a batch hashes serially; that is what the single-frame calls are for."""
+    level, accel = _parse_level(parse, compression_level)
+    req = max(-1, min(int(block_size), 8))   # beyond 7 it is no block size whatever the input's length
+    with _on(stream):
+        off, ln, src_total = _spans(src, src_off, src_len, "src")
+        dev = src.device
+        n = off.numel()
+        if n == 0:
+            e = torch.empty(0, dtype=torch.int64, device=dev)
+            return torch.empty(0, dtype=torch.uint8, device=dev), e, e.clone()
+        bsid, nblocks, linked = N.frames_plan(ln, n, req, block_linked)
+        base = N.exclusive_scan(nblocks)
+        nb, bad, top, n_linked = torch.stack([base[-1], (bsid < 0).sum(), bsid.max(), linked.sum()]).tolist()
+        if bad:
+            raise RuntimeError("LZ4F_compressFrame failed with code: ERROR_maxBlockSize_invalid")
+        hashes = None
+        if content_checksum:                                   # lz4frame.c:1042, 1170-1176
+            hashes = torch.empty(n, dtype=torch.int32, device=dev)
+            N.launch_xxh32_batch(src, off, ln, 0, hashes, n)
+        if nb:
+            P = N.frames_plan_blocks(off, ln, bsid, linked, base, n, nb)
+            cmp_off = N.exclusive_scan(P["slot_len"])
+            cmp = torch.empty(src_total + src_total // 255 + 17 * nb + 64, dtype=torch.uint8, device=dev)
+            cmp_len = torch.zeros(nb, dtype=torch.int32, device=dev)
+            _compress_blocks(src, P, cmp, cmp_off[:nb].contiguous(), cmp_len, parse, level, accel,
+                             bsid, linked, _BLOCK_SIZES[top], n_linked)
+            rec_len = torch.empty(nb, dtype=torch.int32, device=dev)
+            N.frame_block_sizes(P["raw_len"], cmp_len, block_checksum, rec_len, nb)
+            rec_off = N.exclusive_scan(rec_len)
+        else:
+            rec_off = torch.zeros(1, dtype=torch.int64, device=dev)
+        hsize, fsize = N.frames_sizes(rec_off, base, ln, store_size, content_checksum, n)
+        fend = torch.cumsum(fsize, 0)
+        frame_off = fend - fsize
+        total = int(fend[-1])
+        frames = torch.empty(total + 16, dtype=torch.uint8, device=dev)
+        if nb:
+            shift = frame_off + hsize - rec_off[base[:-1]]     # frame position of a frame's first record
+            blk_off = rec_off[:nb] + shift[P["owner"]]
+            N.frame_emit(src, P["raw_off"], P["raw_len"], cmp, cmp_off, cmp_len, frames, blk_off, block_checksum, nb)
+        N.frames_emit(frames, frame_off, fsize, bsid, linked, ln, store_size, block_checksum, content_checksum,
+                      hashes, n)
+        return frames[:total], frame_off, fsize
+
+
+def _compress_blocks(src, P, cmp, cmp_off, cmp_len, parse, level, accel, bsid, linked, max_block, n_linked):
+    """Compress the planned blocks of all frames into their slots of `cmp`:
+    two launches' worth of groups, picked by a per-block mask."""
+    arrays = (P["raw_off"], P["raw_len"], cmp_off, P["cap"])
+    nb = cmp_len.numel()
+    if parse == "parallel":
+        def small(o, ln, co, cap, out, m):
+            N.launch_compress(src, o, ln, cmp, co, cap, out, m, N.PARSE_PARALLEL, accel)
+
+        def large(o, ln, co, cap, out, m):
+            N.launch_compress(src, o, ln, cmp, co, cap, out, m, N.PARSE_PARALLEL_LARGE, accel, max_len=max_block)
+
+        if max_block <= 65536:                                 # one kind only: no split, no read-back
+            small(*arrays, cmp_len, nb)
+            return
+        big = bsid[P["owner"]] > BLOCKSIZE_MAX64KB
+        _launch_subset(~big, arrays, cmp_len, small)
+        _launch_subset(big, arrays, cmp_len, large)
+        return
+    in_linked = linked[P["owner"]] != 0 if n_linked else None
+    if parse == "hc":
+        def indep(o, ln, co, cap, out, m):
+            N.launch_compress_hc(src, o, ln, cmp, co, cap, out, m, level, max_len=max_block)
+
+        def chained(o, ln, co, cap, hist, out, m):
+            N.launch_compress_hc(src, o, ln, cmp, co, cap, out, m, level, max_len=max_block, dict_len=hist)
+
+        if in_linked is None:
+            indep(*arrays, cmp_len, nb)
+            return
+        _launch_subset(~in_linked, arrays, cmp_len, indep)
+        _launch_subset(in_linked, arrays + (P["hist"],), cmp_len, chained)
+        return
+
+    def indep(o, ln, co, cap, out, m):                         # lz4frame.c:853-863
+        N.launch_compress(src, o, ln, cmp, co, cap, out, m, N.TABLE_AUTO, accel)
+
+    def chained(o, ln, co, cap, link, out, m):                 # lz4frame.c:865-871
+        spec = n_linked < _BATCH_SPEC_MAX_FRAMES and m >= _SPEC_MIN_BLOCKS * n_linked
+        N.launch_compress_linked(src, o, ln, link, cmp, co, cap, out, m, accel,
+                                 mode=N.LINKED_SPECULATIVE if spec else N.LINKED_SERIAL)
+
+    if in_linked is None:
+        indep(*arrays, cmp_len, nb)
+        return
+    _launch_subset(~in_linked, arrays, cmp_len, indep)
+    _launch_subset(in_linked, arrays + (P["link"],), cmp_len, chained)
+
+
+def decompress_batch(frames, frame_off, frame_len, *, stream=None):
+    """decompress_device for n frames in one call: frame i is the
+    frame_len[i] bytes at frames[frame_off[i]] of a uint8 device tensor
+    (bytes after a frame's end are allowed).  Returns (out, out_off, out_len,
+    status, bytes_read), device tensors: status[i] == 0 exactly when
+    ``decompress`` of those bytes succeeds; then
+    out[out_off[i] : out_off[i] + out_len[i]] is its result and bytes_read[i]
+    the bytes it consumed.  A skippable frame has status 0 and length 0.  A
+    non-zero status is a code of include/lz4m.h (LZ4M_FRAME_*): a malformed or
+    truncated frame, a block that does not decode, a block or content
+    checksum mismatch, a stored content size that differs; that frame's output
+    span is then unspecified.  No frame's failure changes another frame.
+
+    Two passes find the blocks (lz4m_frames_scan, lz4m_frames_records); the
+    blocks of independent frames decode in one launch into slots of their
+    frame's block size, linked frames one wavefront per frame
+    (lz4m_decompress_chains); one gather packs the blocks of every frame
+    back to back (a block may decode short of the block size) and takes stored
+    blocks from the frame.  Checksums are verified on the device; the content
+    hash is four lanes per frame."""
+    with _on(stream):
+        off, ln, _ = _spans(frames, frame_off, frame_len, "frames")
+        dev = frames.device
+        n = off.numel()
+        if n == 0:
+            e64 = lambda: torch.empty(0, dtype=torch.int64, device=dev)   # noqa: E731
+            return (torch.empty(0, dtype=torch.uint8, device=dev), e64(), e64(),
+                    torch.empty(0, dtype=torch.int32, device=dev), e64())
+        S = N.frames_scan(frames, off, ln, n)
+        base = N.exclusive_scan(S["nblocks"])
+        flags = S["flags"]
+        maxb = torch.ones_like(S["content_size"]) << (8 + 2 * S["bsid"].to(torch.int64))
+        fcap = S["nblocks"].to(torch.int64) * maxb
+        slot_end = torch.cumsum(fcap, 0)
+        slot_base = slot_end - fcap
+        nb, slot_total, any_bc, any_cc = torch.stack([
+            base[-1], slot_end[-1], (flags & N.FRAME_BLOCK_CHECKSUM).sum(),
+            (flags & N.FRAME_CONTENT_CHECKSUM).sum()]).tolist()
+        status = torch.where(S["status"] == N.FRAME_SKIPPABLE, torch.zeros_like(S["status"]), S["status"])
+        if nb:
+            R = N.frames_records(frames, off, ln, S, base, slot_base, n, nb)
+            owner = R["frame"]
+            chain = ((flags & N.FRAME_LINKED) != 0) & (S["nblocks"] > 1)   # lz4frame.c:1853-1856
+            in_chain = chain[owner]
+            stored = (R["raw"] != 0) & ~in_chain
+            slots = torch.empty(slot_total + 16, dtype=torch.uint8, device=dev)
+            blk = torch.empty(nb, dtype=torch.int32, device=dev)
+            # stored blocks and the chains' blocks go to the decoder with length 0 (rejected at once, no work)
+            dec_len = torch.where(stored | in_chain, torch.zeros_like(R["len"]), R["len"])
+            N.launch_decompress(frames, R["pos"], dec_len, slots, R["slot_off"], R["slot_cap"], blk, nb)
+            count = torch.where(chain, S["nblocks"], torch.zeros_like(S["nblocks"]))
+            N.launch_decompress_chains(frames, R["pos"], R["len"], R["raw"], base, count, slots, slot_base,
+                                       maxb.to(torch.int32), blk, n)
+            size = torch.where(stored, R["len"], blk.clamp(min=0))
+            bad = ((blk < 0) & ~stored).to(torch.int32)
+            goff = N.exclusive_scan(size)
+            out_off = goff[base[:-1]]
+            out_len = goff[base[1:]] - out_off
+            out_total = int(goff[-1])
+            out = torch.empty(out_total + 16, dtype=torch.uint8, device=dev)
+            # a chain wrote its blocks back to back from its frame's first slot
+            from_slot = torch.where(in_chain, slot_base[owner] + (goff[:nb] - out_off[owner]), R["slot_off"])
+            zero = torch.zeros_like(size)
+            N.gather(slots, from_slot, torch.where(stored, zero, size), out, goff, nb)
+            N.gather(frames, R["pos"], torch.where(stored, size, zero), out, goff, nb)
+            fbad = torch.zeros(n, dtype=torch.int32, device=dev).index_add_(0, owner, bad)
+            status = torch.where((status == 0) & (fbad > 0), torch.full_like(status, N.FRAME_BLOCK_FAILED), status)
+            if any_bc:                                         # lz4frame.c:1819
+                sums = torch.empty(nb, dtype=torch.int32, device=dev)
+                N.launch_xxh32_batch(frames, R["pos"], R["len"].to(torch.int64), 0, sums, nb)
+                crc_bad = (R["crc"] >= 0) & _crc_mismatch(frames, sums, R["crc"].clamp(min=0))
+                fcrc = torch.zeros(n, dtype=torch.int32, device=dev).index_add_(0, owner, crc_bad.to(torch.int32))
+                status = torch.where((status == 0) & (fcrc > 0),
+                                     torch.full_like(status, N.FRAME_BLOCK_CHECKSUM_BAD), status)
+        else:
+            out = torch.empty(16, dtype=torch.uint8, device=dev)
+            out_total = 0
+            out_off = torch.zeros(n, dtype=torch.int64, device=dev)
+            out_len = torch.zeros(n, dtype=torch.int64, device=dev)
+        wrong = (S["content_size"] != 0) & (S["content_size"] != out_len)      # lz4frame.c:1927
+        status = torch.where((status == 0) & wrong, torch.full_like(status, N.FRAME_CONTENT_SIZE_WRONG), status)
+        if any_cc:                                             # lz4frame.c:1850, 1959-1964
+            sums = torch.empty(n, dtype=torch.int32, device=dev)
+            N.launch_xxh32_batch(out, out_off, out_len, 0, sums, n)
+            cc_bad = (S["cpos"] >= 0) & _crc_mismatch(frames, sums, S["cpos"].clamp(min=0))
+            status = torch.where((status == 0) & cc_bad, torch.full_like(status, N.FRAME_CONTENT_CHECKSUM_BAD),
+                                 status)
+        return out[:out_total], out_off, out_len, status, S["end"]
+
+
+def _stage_many(views):
+    """The buffers packed back to back on the device through the block API's
+    pinned staging (one host-to-device copy): (device bytes, int64 offsets,
+    int32 lengths)."""
+    from ..block import _block as B
+    lens = [v.nbytes for v in views]
+    zeros = [0] * len(views)
+    lay, _h, d = B._stage_in(N.device(), views, B._excl_offsets(lens), lens, zeros, zeros)
+    buf, d_off, d_len = B._dev_views(lay, d, len(views))[:3]
+    return buf[:sum(lens)] if sum(lens) else buf[:0], d_off, d_len
+
+
+def compress_many(datas, compression_level=0, block_size=0, content_checksum=False, block_checksum=False,
+                  block_linked=True, store_size=True, return_bytearray=False):
+    """[compress(d, ...) for d in datas] in one batched call (compress_batch
+    on the inputs packed into one staging copy).  Levels >= 3 raise what
+    ``compress`` raises."""
+    views = [_buffer(d, "data") for d in datas]
+    level = _c_int(compression_level, "compression_level")
+    bsid_req = _c_int(block_size, "block_size")
+    if not views:
+        return []
+    if max(v.nbytes for v in views) > 0x7FFFFFFF:   # a frame beyond the staging tables: the single-frame path
+        return [compress(v, level, bsid_req, content_checksum, block_checksum, block_linked, store_size,
+                         return_bytearray) for v in views]
+    N.device()
+    _parse_level("exact", level)
+    buf, d_off, d_len = _stage_many(views)
+    frames, f_off, f_len = compress_batch(buf, d_off, d_len, compression_level=level, block_size=bsid_req,
+                                          content_checksum=content_checksum, block_checksum=block_checksum,
+                                          block_linked=block_linked, store_size=store_size)
+    return _unpack_many(frames, f_off, f_len, bool(return_bytearray))
+
+
+def _unpack_many(buf, off, length, as_bytearray):
+    """New bytes objects of the spans of a device buffer (one device-to-host copy, one pooled host copy)."""
+    from ..block import _block as B
+    host = buf.cpu().numpy()
+    return B._results_many(host, off.cpu().tolist(), length.cpu().tolist(), None, as_bytearray)
+
+
+def decompress_many(frames, return_bytearray=False, return_bytes_read=False):
+    """[decompress(f, ...) for f in frames] in one batched call
+    (decompress_batch).  If a frame fails, the lowest failing index raises
+    what ``decompress`` raises for its bytes."""
+    views = [_buffer(f, "data") for f in frames]
+    if not views:
+        return []
+    if max(v.nbytes for v in views) > 0x7FFFFFFF:
+        return [decompress(v, return_bytearray, return_bytes_read) for v in views]
+    buf, d_off, d_len = _stage_many(views)
+    out, o_off, o_len, status, read = decompress_batch(buf, d_off, d_len)
+    st = status.cpu().tolist()
+    for i, s in enumerate(st):
+        if s != 0:
+            decompress(views[i])                               # raises the single call's error
+            raise RuntimeError(f"lz4.frame.decompress_many: frame {i} failed with batch status {s}, "
+                               "but decompress accepts it")
+    res = _unpack_many(out, o_off, o_len, bool(return_bytearray))
+    if return_bytes_read:
+        return list(zip(res, read.cpu().tolist()))
+    return res
