@@ -145,6 +145,43 @@ int lz4m_pcompress_large_batch(const uint8_t* d_src, const int64_t* d_src_off, c
                                lz4m_stream_t stream);
 
 /*
+ * LZ4M_PARSE_PARALLEL with one dictionary shared by every block of the batch
+ * (many small blocks, one trained dictionary; no reference counterpart: the
+ * reference loads the dictionary into a stream per block, lz4.c:1541-1581).
+ * d_dict points at the whole dictionary of dict_len bytes, stored once
+ * anywhere in device memory; its last min(dict_len, 65536) bytes count.
+ * lz4m_pcompress_dict_prepare hashes them, once per dictionary, into d_table:
+ * lz4m_pcompress_dict_table_bytes() = 8192 bytes of device memory, 16-byte
+ * aligned -- the parse's 4096-entry u16 table as the positions of the
+ * dictionary that have their hashed bytes inside it (the rule of
+ * LZ4_loadDict; this parse hashes five bytes) leave it.
+ * lz4m_pcompress_dict_batch then compresses n blocks laid out as
+ * for lz4m_compress_batch, each wavefront starting from a copy of that table:
+ * matches may start in the dictionary (offsets up to 65535; such a match ends
+ * at the dictionary's end at the latest), and every block decodes with
+ * LZ4_decompress_safe_usingDict over the dictionary
+ * (lz4m_decompress_batch_dict).  Valid blocks, NOT byte-identical to
+ * lz4.block.compress(dict=); with dict_len < 4 the bytes of
+ * lz4m_compress_batch with LZ4M_PARSE_PARALLEL.  Blocks longer than 65536
+ * bytes report 0; d_out_len[i] = 0 also when the block does not fit
+ * d_dst_cap[i] (an exact fit is accepted, nothing is written past the
+ * capacity).  d_table must be the table prepared from the same d_dict and
+ * dict_len (any other table still gives valid blocks, of any size).  Both
+ * calls are stream-ordered, allocate nothing and do not synchronise; one
+ * launch each.  LZ4M_EINVAL, before any HIP call: dict_len < 0; a null or
+ * misaligned table or table_bytes below lz4m_pcompress_dict_table_bytes()
+ * (prepare); n < 0, a misaligned table, or a null table or dictionary with
+ * dict_len > 0 (batch).  n == 0 returns 0.
+ */
+size_t lz4m_pcompress_dict_table_bytes(void);
+int lz4m_pcompress_dict_prepare(const uint8_t* d_dict, int64_t dict_len, void* d_table, size_t table_bytes,
+                                lz4m_stream_t stream);
+int lz4m_pcompress_dict_batch(const uint8_t* d_src, const int64_t* d_src_off, const int32_t* d_src_len,
+                              const uint8_t* d_dict, int64_t dict_len, const void* d_table, uint8_t* d_dst,
+                              const int64_t* d_dst_off, const int32_t* d_dst_cap, int32_t* d_out_len, int64_t n,
+                              lz4m_stream_t stream);
+
+/*
  * Batched lz4.block.compress(mode="high_compression", compression=level)
  * (_block.c:112-119 -> LZ4_compress_HC_continue on a fresh stream): a
  * hash-chain ("HC") parse on the device (lz4m_hc.hip).  Every result is a

@@ -37,6 +37,11 @@ namespace lz4m {
 int pcompress_launch(const uint8_t* d_src, const int64_t* d_src_off, const int32_t* d_src_len, uint8_t* d_dst,
                      const int64_t* d_dst_off, const int32_t* d_dst_cap, int32_t* d_out_len, int64_t n, int variant,
                      hipStream_t stream);
+int pcompress_dict_prepare_launch(const uint8_t* d_dict, int64_t dict_len, void* d_table, hipStream_t stream);
+int pcompress_dict_launch(const uint8_t* d_src, const int64_t* d_src_off, const int32_t* d_src_len,
+                          const uint8_t* d_dict, int64_t dict_len, const void* d_table, uint8_t* d_dst,
+                          const int64_t* d_dst_off, const int32_t* d_dst_cap, int32_t* d_out_len, int64_t n,
+                          hipStream_t stream);
 
 constexpr int kMinLength = 13;        // lz4.c:247
 constexpr int kLimit64K = 65536 + 11; // lz4.c:689
@@ -1448,6 +1453,34 @@ extern "C" int lz4m_compress_batch(const uint8_t* d_src, const int64_t* d_src_of
             return LZ4M_EINVAL;
     }
     return (int)hipGetLastError();
+}
+
+// LZ4M_PARSE_PARALLEL with one shared dictionary (lz4m_pcompress.hip).  The
+// table: 4096 u16 entries, 16-byte aligned for the kernel's 16-byte loads.
+constexpr size_t kPdictTableBytes = 8192;
+
+extern "C" size_t lz4m_pcompress_dict_table_bytes(void) { return kPdictTableBytes; }
+
+extern "C" int lz4m_pcompress_dict_prepare(const uint8_t* d_dict, int64_t dict_len, void* d_table, size_t table_bytes,
+                                           lz4m_stream_t stream) {
+    if (dict_len < 0 || table_bytes < kPdictTableBytes || d_table == nullptr || ((uintptr_t)d_table & 15) != 0 ||
+        (dict_len > 0 && d_dict == nullptr))
+        return LZ4M_EINVAL;
+    if (const int e = lds_order_check()) return e;
+    return pcompress_dict_prepare_launch(d_dict, dict_len, d_table, (hipStream_t)stream);
+}
+
+extern "C" int lz4m_pcompress_dict_batch(const uint8_t* d_src, const int64_t* d_src_off, const int32_t* d_src_len,
+                                         const uint8_t* d_dict, int64_t dict_len, const void* d_table, uint8_t* d_dst,
+                                         const int64_t* d_dst_off, const int32_t* d_dst_cap, int32_t* d_out_len,
+                                         int64_t n, lz4m_stream_t stream) {
+    if (n < 0 || dict_len < 0 || ((uintptr_t)d_table & 15) != 0 ||
+        (dict_len > 0 && (d_dict == nullptr || d_table == nullptr)))
+        return LZ4M_EINVAL;
+    if (n == 0) return 0;
+    if (const int e = lds_order_check()) return e;
+    return pcompress_dict_launch(d_src, d_src_off, d_src_len, d_dict, dict_len, d_table, d_dst, d_dst_off, d_dst_cap,
+                                 d_out_len, n, (hipStream_t)stream);
 }
 
 static int compress_dict_launch(const uint8_t* d_src, const int64_t* d_src_off, const int32_t* d_src_len,

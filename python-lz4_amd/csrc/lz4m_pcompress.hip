@@ -33,6 +33,11 @@
 // The kernel is bound by instruction issue (VALU ~0.75 per CU-cycle, PMC):
 // every step above is written to keep both the VALU and the per-CU scalar
 // unit short.
+//
+// With one dictionary shared by every block of a batch
+// (lz4m_pcompress_dict_batch) the table starts as the dictionary's, prepared
+// once (pcompress_dict_prepare_kernel), and candidates may lie in the
+// dictionary: the DICT instantiation, DESIGN.md section 3.8.
 #include "lz4m_common.h"
 
 #include <stdlib.h>
@@ -98,13 +103,26 @@ __device__ __forceinline__ int32_t count_below(uint64_t m) {
 
 // Wave-cooperative forward match length of s[a..] vs s[c..] (c < a), at most
 // `lim` bytes; a + lim <= n - 5, so every 4-byte read stays in the block.
-__device__ __forceinline__ int32_t wave_count(const uint8_t* s, int32_t a, int32_t c, int32_t lim, uint32_t lane) {
+// EXT (the dictionary parse): the candidate is cb[c..] in another buffer that
+// ends at cb[c + lim] at the earliest, and no read of it passes that end.
+template <bool EXT = false>
+__device__ __forceinline__ int32_t wave_count(const uint8_t* s, int32_t a, int32_t c, int32_t lim, uint32_t lane,
+                                              const uint8_t* cb = nullptr) {
+    const uint8_t* sc = EXT ? cb : s;
     int32_t done = 0;
     {   // the first 256 bytes: 4 per lane (most long matches end here)
         const int32_t k = 4 * (int32_t)lane;
         int32_t e = 0;   // equal bytes in this lane's dword (4 = all)
         if (k < lim) {
-            const uint32_t x = ld32(s + a + k) ^ ld32(s + c + k);
+            const uint32_t xa = ld32(s + a + k);
+            uint32_t y;
+            if (EXT && lim - k < 4) {   // the last bytes before the buffer's end
+                y = 0;
+                for (int32_t q = 0; q < lim - k; ++q) y |= (uint32_t)sc[c + k + q] << (8 * q);
+            } else {
+                y = ld32(sc + c + k);
+            }
+            const uint32_t x = xa ^ y;
             e = x ? (int32_t)(__builtin_ctz(x) >> 3) : 4;
             const int32_t nb = lim - k < 4 ? lim - k : 4;
             if (e > nb) e = nb;
@@ -126,7 +144,7 @@ __device__ __forceinline__ int32_t wave_count(const uint8_t* s, int32_t a, int32
         if (k < lim) {
             const int32_t nb = lim - k < 16 ? lim - k : 16;
             const u32x4 x = nb == 16 ? ld16(s + a + k) : ld16_guarded(s + a + k, nb);
-            const u32x4 y = nb == 16 ? ld16(s + c + k) : ld16_guarded(s + c + k, nb);
+            const u32x4 y = nb == 16 ? ld16(sc + c + k) : ld16_guarded(sc + c + k, nb);
             e = (int32_t)eq_prefix16(x, y);
             if (e > nb) e = nb;
         }
@@ -236,6 +254,35 @@ __device__ __forceinline__ uint32_t load_word(const uint8_t* s, int32_t p, int32
     return x;
 }
 
+// The dictionary parse keys its table by five bytes:
+// the 12-bit hash4 of bytes [p, p + 4), mixed with byte p + 4.  A position's
+// word is then bytes [p, p + 5) (zero past n) in a u64.
+template <bool DICT>
+struct PosWord {
+    typedef uint32_t type;
+};
+template <>
+struct PosWord<true> {
+    typedef uint64_t type;
+};
+__device__ __forceinline__ uint64_t load_word5(const uint8_t* s, int32_t p, int32_t n) {
+    if (p + 8 <= n) return ld64(s + (uint32_t)p);
+    uint64_t x = 0;
+    for (int k = 0; k < 5; ++k)
+        if (p + k < n) x |= (uint64_t)s[p + k] << (8 * k);
+    return x;
+}
+template <bool DICT>
+__device__ __forceinline__ typename PosWord<DICT>::type load_pos(const uint8_t* s, int32_t p, int32_t n) {
+    if constexpr (DICT)
+        return load_word5(s, p, n);
+    else
+        return load_word(s, p, n);
+}
+__device__ __forceinline__ uint32_t hash5_12(uint32_t v, uint32_t b4) {
+    return hash4<12>(v) ^ (((b4 & 0xFFu) * 37u) & 0xFFFu);
+}
+
 // Candidates of one 64-position chunk; the verify loads are issued here and
 // consumed by chunk_finish, so their latency overlaps the previous chunk's
 // parse and encode.
@@ -260,13 +307,34 @@ struct Chunk {
 // aliases to a position in the window; the 4-byte verify takes it only if its
 // bytes match, and then it is a valid match like any other.  Half the LDS of
 // the u32 table, so twice the waves per CU.
-template <bool BIG, int HB, bool WIN = false>
-__device__ __forceinline__ void chunk_issue(Chunk& C, const uint8_t* s, uint32_t* table32, int32_t p0, uint32_t v,
-                                            int32_t N, int32_t mlast, uint32_t lane) {
+//
+// DICT (lz4m_pcompress_dict_batch, blocks <= 64 KiB): the last t <= 65536
+// bytes of a dictionary lie logically just before the block, at positions
+// -t .. -1 (dend[-k] is the byte at position -k).  The table holds the low 16
+// bits of each position, block or dictionary, and starts as the prepared
+// table of the dictionary (pcompress_dict_prepare_kernel); a candidate is
+// recovered as for WIN, so it lies in [p - 65535, p) -- never at distance
+// 65536 -- and one below -t does not exist.  A dictionary candidate is read
+// from the dictionary and no read passes the dictionary's end; its match
+// ends there at the latest.  The table's key is five
+// bytes, hash5_12 (four gave +5.8 % on source code against the reference's
+// dictionary mode, which hashes five; five give +3.4 %).
+template <bool BIG, int HB, bool WIN = false, bool DICT = false>
+__device__ __forceinline__ void chunk_issue(Chunk& C, const uint8_t* s, uint32_t* table32, int32_t p0,
+                                            typename PosWord<DICT>::type vw, int32_t N, int32_t mlast, uint32_t lane,
+                                            const uint8_t* dend = nullptr, int32_t t = 0) {
+    static_assert(!DICT || (!BIG && !WIN), "the dictionary parse is for blocks up to 64 KiB");
     constexpr bool U32 = BIG && !WIN;   // whole positions in a u32 table
+    constexpr int32_t kNone = DICT ? -(1 << 20) : -1;   // no candidate (below every dictionary position)
+    const uint32_t v = (uint32_t)vw;
     const int32_t p = p0 + (int32_t)lane;
     const bool act = p + 4 <= N;
-    const uint32_t h = act ? hash4<HB>(v) : (1u << HB);
+    uint32_t hv;
+    if constexpr (DICT)
+        hv = hash5_12(v, (uint32_t)(vw >> 32));
+    else
+        hv = hash4<HB>(v);
+    const uint32_t h = act ? hv : (1u << HB);
     // lanes with the same hash (one ballot per hash bit), hence the nearest
     // earlier one (the candidate) and whether a later one exists (then this
     // lane does not write the table)
@@ -281,10 +349,10 @@ __device__ __forceinline__ void chunk_issue(Chunk& C, const uint8_t* s, uint32_t
     if (earlier) {
         cand = p0 + 63 - (int32_t)__builtin_clzll(earlier);
     } else if (old == empty) {
-        cand = -1;
-    } else if (WIN) {   // the most recent earlier position with these low 16 bits (none at distance 0)
+        cand = kNone;
+    } else if (WIN || DICT) {   // the most recent earlier position with these low 16 bits (none at distance 0)
         const int32_t dd = (p - (int32_t)old) & 0xFFFF;
-        cand = dd ? p - dd : -1;
+        cand = dd ? p - dd : kNone;
     } else {
         cand = (int32_t)old;
     }
@@ -297,6 +365,43 @@ __device__ __forceinline__ void chunk_issue(Chunk& C, const uint8_t* s, uint32_t
     }
     C.v = v;
     C.cand = cand;
+    if constexpr (DICT) {
+        // a dictionary candidate has its four bytes inside the dictionary
+        // (the prepared table holds no other; a table that is not this
+        // dictionary's must not lead a read astray either)
+        C.okc = act && cand >= -t && (cand >= 0 || cand <= -4) && p <= mlast;
+        const bool ind = C.okc && cand < 0;
+        // (the position again, from a lane id the compiler takes as new: the
+        // offsets below are then made here, not kept in registers from the
+        // kernel's start on, where they cost this instantiation its 5 waves)
+        uint32_t ln = lane;
+        asm volatile("" : "+v"(ln));
+        const int32_t pl = p0 + (int32_t)ln;
+        const int32_t ps = C.okc ? pl : 0;
+        C.fa = p0 + 84 <= N ? ld16(s + (uint32_t)(ps + 4)) : ld16_guarded(s + ps + 4, N - ps - 4);
+        // the 4 bytes before: inside the candidate's own buffer, and before p
+        // inside the block (a block candidate closer than 4 to the block's
+        // start gets none, as without a dictionary)
+        const bool bk = C.okc && (cand >= 4 || (cand < 0 && cand - 4 >= -t && p >= 4));
+        C.bp = bk ? ld32(s + (uint32_t)(pl - 4)) : 0u;
+        C.bc = 0x80000000u;   // (no bytes before: differs in the byte next to the match)
+        // the candidate's bytes, from its own buffer: each branch takes its
+        // base from SGPRs and an unsigned 32-bit offset, as without a dictionary
+        if (ind) {
+            const uint8_t* d0 = dend - t;
+            const uint32_t co = (uint32_t)(cand + t);
+            C.xc = ld32(d0 + co);
+            // the 16 bytes after the four end with the dictionary
+            C.fc = ld16_guarded(d0 + co + 4, -cand - 4);
+            if (bk) C.bc = ld32(d0 + (co - 4));
+        } else {
+            const int32_t cs = C.okc ? cand : 0;
+            C.xc = ld32(s + (uint32_t)cs);
+            C.fc = p0 + 84 <= N ? ld16(s + (uint32_t)(cs + 4)) : ld16_guarded(s + cs + 4, N - cs - 4);
+            if (bk) C.bc = ld32(s + (uint32_t)(cand - 4));
+        }
+        return;
+    }
     // LZ4_DISTANCE_MAX (lz4.c:1064): only checkable past 64 KiB
     C.okc = act && cand >= 0 && p <= mlast && (!U32 || p - cand <= 65535);
     // every address stays inside the block (N >= 4 here; p <= mlast when okc)
@@ -317,6 +422,7 @@ __device__ __forceinline__ void chunk_issue(Chunk& C, const uint8_t* s, uint32_t
     C.bc = bk ? ld32(s + (uint32_t)(cand - 4)) : 1u;
 }
 
+template <bool DICT = false>
 __device__ __forceinline__ uint64_t chunk_finish(const Chunk& C, int32_t p0, int32_t matchlimit, int32_t& L,
                                                  int32_t& back, uint32_t lane) {
     const int32_t p = p0 + (int32_t)lane;
@@ -324,8 +430,11 @@ __device__ __forceinline__ uint64_t chunk_finish(const Chunk& C, int32_t p0, int
     const bool ok = C.okc && C.xc == C.v && lim >= 4;
     L = 4 + (int32_t)eq_prefix16(C.fa, C.fc);
     if (L > lim) L = lim;
+    // a match from the dictionary ends at the dictionary's end (-cand >= 4 bytes)
+    if (DICT && C.cand < 0 && L > -C.cand) L = -C.cand;
     const uint32_t x = C.bp ^ C.bc;
-    back = C.cand >= 4 ? (x ? (int32_t)(__builtin_clz(x) >> 3) : 4) : 0;
+    // (DICT: chunk_issue's bc says where there are no bytes to look back at)
+    back = DICT || C.cand >= 4 ? (x ? (int32_t)(__builtin_clz(x) >> 3) : 4) : 0;
     return __ballot(ok);
 }
 
@@ -358,7 +467,10 @@ __host__ __device__ inline int32_t seg_count(int32_t n) {
     return (int32_t)(((int64_t)n + seg - 1) / seg);
 }
 
-template <bool BIG, int HB, bool WIN = false, bool SEG = false>
+// DICT (lz4m_pcompress_dict_batch: LZ4M_PARSE_PARALLEL with one dictionary
+// for every block of the batch): dend = the dictionary's end, t = the bytes
+// of it that count (4..65536), prep = its prepared table (8 KiB).
+template <bool BIG, int HB, bool WIN = false, bool SEG = false, bool DICT = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((BIG && !WIN) || HB > 12 ? 1 : 5))) void pcompress_kernel(const uint8_t* __restrict__ src,
                                                        const int64_t* __restrict__ src_off,
                                                        const int32_t* __restrict__ src_len, uint8_t* __restrict__ dst,
@@ -366,14 +478,21 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((BIG && !WIN
                                                        const int32_t* __restrict__ dst_cap,
                                                        int32_t* __restrict__ out_len, int64_t n,
                                                        int32_t* __restrict__ seg_meta = nullptr, int64_t seg_cap = 0,
-                                                       int32_t segs = 1) {
+                                                       int32_t segs = 1, const uint8_t* __restrict__ dend = nullptr,
+                                                       int32_t t = 0, const u32x4* __restrict__ prep = nullptr) {
     static_assert(!SEG || (BIG && WIN), "segments are parsed with the windowed table");
+    static_assert(!DICT || (!BIG && HB == 12 && !WIN && !SEG), "the dictionary parse: blocks <= 64 KiB, 12-bit table");
     // 8192 hash4 entries: u16 positions (blocks <= 64 KiB) or u32 (BIG)
     constexpr int kWords = (BIG && !WIN) ? (1 << HB) : (1 << HB) / 2;   // table size in u32 words
     __shared__ __attribute__((aligned(16))) uint32_t table[kWords];
-    const uint32_t lane = threadIdx.x;
+    const uint32_t lane_k = threadIdx.x;
     const int64_t items = SEG ? n * segs : n;
     for (int64_t b = blockIdx.x; b < items; b += gridDim.x) {
+        // (DICT: a lane id the compiler takes as new in every block, so that
+        // what it derives from it is made where it is used and not kept in
+        // registers across the loop: that instantiation has none to spare)
+        uint32_t lane = lane_k;
+        if constexpr (DICT) asm volatile("" : "+v"(lane));
         int32_t N, cap, lo = 0, mlast, matchlimit;
         bool fin = true;
         const uint8_t* s;
@@ -412,8 +531,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((BIG && !WIN
             mlast = N - 12;      // last match start (MFLIMIT)
             matchlimit = N - 5;  // match end bound (LASTLITERALS)
         }
-        for (int k = (int)lane; k < kWords / 4; k += 64)
-            reinterpret_cast<u32x4*>(table)[k] = u32x4{0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+        // an empty table, or the dictionary's (8 KiB, shared by every block: L2-resident)
+        if constexpr (DICT) {
+            // 16 bytes per lane and step: a uniform base per step and the
+            // lane's unsigned 32-bit offset (no per-lane 64-bit addresses)
+            const uint8_t* pb = reinterpret_cast<const uint8_t*>(prep);
+#pragma unroll
+            for (int i = 0; i < kWords / 256; ++i)
+                reinterpret_cast<u32x4*>(table)[64 * i + (int)lane] = ld16(pb + 1024 * i + (uint32_t)(16 * lane));
+        } else {
+            for (int k = (int)lane; k < kWords / 4; k += 64)
+                reinterpret_cast<u32x4*>(table)[k] = u32x4{0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+        }
         int32_t anchor = lo, cur = lo, op = 0;
         int32_t f_lit = -1, f_ml = 0;   // SEG: the first sequence's literal and match lengths
         bool fail = false;
@@ -421,11 +550,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((BIG && !WIN
         Chunk A;
         int32_t L = 0, back = 0;
         uint64_t mask = 0;
-        uint32_t wnext = 0;   // the hash word of the chunk after next, loaded a chunk ahead
+        typename PosWord<DICT>::type wnext = 0;   // the hash word of the chunk after next, loaded a chunk ahead
         if (N - lo >= 4) {
-            chunk_issue<BIG, HB, WIN>(A, s, table, lo, load_word(s, lo + (int32_t)lane, N), N, mlast, lane);
-            mask = chunk_finish(A, lo, matchlimit, L, back, lane);
-            if (lo + 68 <= N) wnext = load_word(s, lo + 64 + (int32_t)lane, N);
+            chunk_issue<BIG, HB, WIN, DICT>(A, s, table, lo, load_pos<DICT>(s, lo + (int32_t)lane, N), N, mlast, lane,
+                                            dend, t);
+            mask = chunk_finish<DICT>(A, lo, matchlimit, L, back, lane);
+            if (lo + 68 <= N) wnext = load_pos<DICT>(s, lo + 64 + (int32_t)lane, N);
         }
         // Per chunk: issue B's loads (and the word of the chunk after B),
         // walk A, finish B, then encode A.  No store sits between a load and
@@ -434,14 +564,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((BIG && !WIN
         for (int32_t p0 = lo; p0 + 4 <= N; p0 += 64) {
             const bool has_next = p0 + 68 <= N;
             Chunk B;
-            uint32_t wafter = 0;
+            typename PosWord<DICT>::type wafter = 0;
             // B's loads are issued after A's walk, whose
             // long-match counts and catch-up loads wait at once (gfx9 counts
             // loads in order: such a wait would also wait for B's)
             auto issue_b = [&]() __attribute__((always_inline)) {
                 if (has_next) {
-                    chunk_issue<BIG, HB, WIN>(B, s, table, p0 + 64, wnext, N, mlast, lane);
-                    if (p0 + 132 <= N) wafter = load_word(s, p0 + 128 + (int32_t)lane, N);
+                    chunk_issue<BIG, HB, WIN, DICT>(B, s, table, p0 + 64, wnext, N, mlast, lane, dend, t);
+                    if (p0 + 132 <= N) wafter = load_pos<DICT>(s, p0 + 128 + (int32_t)lane, N);
                 }
             };
             // ---- greedy parse of chunk p0.  The serial walk only picks the
@@ -457,7 +587,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((BIG && !WIN
             while (rem) {
                 const int j = __builtin_ctzll(rem);
                 int32_t len = rdl(L, j);
-                if (len == 20 && len < matchlimit - (p0 + j)) {
+                if constexpr (DICT) {
+                    // the same count; a dictionary candidate's bytes end with the dictionary
+                    const int32_t cj = rdl(A.cand, j);
+                    int32_t more = matchlimit - (p0 + j) - 20;
+                    if (cj < 0 && more > -cj - 20) more = -cj - 20;
+                    if (len == 20 && more > 0) {
+                        len = 20 + wave_count<true>(s, p0 + j + 20, cj + 20, more, lane, cj < 0 ? dend : s);
+                        if ((int)lane == j) Lx = len;
+                    }
+                } else if (len == 20 && len < matchlimit - (p0 + j)) {
                     len = 20 + wave_count(s, p0 + j + 20, rdl(A.cand, j) + 20, matchlimit - (p0 + j) - 20, lane);
                     if ((int)lane == j) Lx = len;
                 }
@@ -483,7 +622,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((BIG && !WIN
                 int32_t st = p, c = A.cand, len = Lx, bk = back;
                 if (isch) {
                     if (bk > st - anc) bk = st - anc;
-                    if (bk == 4) {
+                    if constexpr (DICT) {
+                        // the source stays in the buffer it starts in
+                        if (bk == 4) {
+                            if (c < 0) {
+                                const uint8_t* d0 = dend - t;
+                                const int32_t cc = c + t;
+                                while (st - bk > anc && cc - bk > 0 && s[st - bk - 1] == d0[(uint32_t)(cc - bk - 1)])
+                                    ++bk;
+                            } else {
+                                while (st - bk > anc && c - bk > 0 && s[st - bk - 1] == s[c - bk - 1]) ++bk;
+                            }
+                        }
+                    } else if (bk == 4) {
                         while (st - bk > anc && c - bk > 0 && s[st - bk - 1] == s[c - bk - 1]) ++bk;
                     }
                 }
@@ -532,7 +683,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((BIG && !WIN
                 }
                 op += w;
             }
-            if (has_next) maskB = chunk_finish(B, p0 + 64, matchlimit, LB, backB, lane);
+            if (has_next) maskB = chunk_finish<DICT>(B, p0 + 64, matchlimit, LB, backB, lane);
             if (!has_next) break;
             vprev = A.v;
             A.v = B.v;
@@ -560,6 +711,43 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((BIG && !WIN
             else
                 out_len[b] = fail ? 0 : op;
         }
+    }
+}
+
+// The dictionary's table, once per dictionary: what the parse loop leaves
+// behind after the positions -t .. -5 (those with their five hashed bytes
+// inside the dictionary: LZ4_loadDict's rule, lz4.c:1575-1579, for a key of
+// five bytes), i.e. for each hash the low 16 bits of the last such position,
+// 0xFFFF where there is none.
+// kPrepWaves wavefronts take consecutive runs of 64-position chunks, each into
+// its own LDS table by the parse's chunk step (one writer per hash); the
+// table of the last run that has an entry wins.  t < 5: an empty table.
+constexpr int kPrepWaves = 4;
+
+__global__ __launch_bounds__(64 * kPrepWaves) void pcompress_dict_prepare_kernel(const uint8_t* __restrict__ dend,
+                                                                                 int32_t t,
+                                                                                 uint16_t* __restrict__ out) {
+    __shared__ uint16_t tabs[kPrepWaves][1 << 12];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
+    for (uint32_t e = tid; e < (uint32_t)kPrepWaves << 12; e += 64 * kPrepWaves) (&tabs[0][0])[e] = (uint16_t)kEmpty;
+    __syncthreads();
+    const int32_t npos = t >= 5 ? t - 4 : 0;   // positions with their five hashed bytes
+    const int32_t per = ((npos + 64 * kPrepWaves - 1) / (64 * kPrepWaves)) * 64;
+    const int32_t hi = npos < (int32_t)(w + 1) * per ? npos : (int32_t)(w + 1) * per;
+    const uint8_t* d0 = dend - t;
+    for (int32_t j0 = (int32_t)w * per; j0 < hi; j0 += 64) {
+        const int32_t j = j0 + (int32_t)lane;
+        const bool act = j < hi;
+        const uint32_t h = act ? hash5_12(ld32(d0 + j), d0[j + 4]) : (1u << 12);
+        const uint64_t eq = same_hash_mask<12>(h, act);
+        if (act && (eq >> lane) <= 1u) tabs[w][h] = (uint16_t)(j - t);
+    }
+    __syncthreads();
+    for (uint32_t e = tid; e < (1u << 12); e += 64 * kPrepWaves) {
+        uint32_t v = kEmpty;
+        for (int k = 0; k < kPrepWaves; ++k)
+            if (tabs[k][e] != kEmpty) v = tabs[k][e];
+        out[e] = (uint16_t)v;
     }
 }
 
@@ -699,6 +887,30 @@ int pcompress_launch(const uint8_t* d_src, const int64_t* d_src_off, const int32
         hipLaunchKernelGGL((pcompress_kernel<false, 12>), dim3(grid), dim3(64), 0, stream, d_src, d_src_off,
                            d_src_len, d_dst, d_dst_off, d_dst_cap, d_out_len, n);
     }
+    return (int)hipGetLastError();
+}
+
+// lz4m_pcompress_dict_prepare / _batch after their argument checks
+// (lz4m_compress.hip).  d_dict: the whole dictionary; its last 64 KiB count.
+int pcompress_dict_prepare_launch(const uint8_t* d_dict, int64_t dict_len, void* d_table, hipStream_t stream) {
+    const int32_t t = (int32_t)(dict_len < 65536 ? dict_len : 65536);
+    hipLaunchKernelGGL(pcompress_dict_prepare_kernel, dim3(1), dim3(64 * kPrepWaves), 0, stream, d_dict + dict_len, t,
+                       (uint16_t*)d_table);
+    return (int)hipGetLastError();
+}
+
+int pcompress_dict_launch(const uint8_t* d_src, const int64_t* d_src_off, const int32_t* d_src_len,
+                          const uint8_t* d_dict, int64_t dict_len, const void* d_table, uint8_t* d_dst,
+                          const int64_t* d_dst_off, const int32_t* d_dst_cap, int32_t* d_out_len, int64_t n,
+                          hipStream_t stream) {
+    // below 4 bytes a dictionary holds no position: the parse without one
+    if (dict_len < 4)
+        return pcompress_launch(d_src, d_src_off, d_src_len, d_dst, d_dst_off, d_dst_cap, d_out_len, n, 0, stream);
+    const int32_t t = (int32_t)(dict_len < 65536 ? dict_len : 65536);
+    const uint32_t grid = (uint32_t)(n < (1ll << 30) ? n : (1ll << 30));
+    hipLaunchKernelGGL((pcompress_kernel<false, 12, false, false, true>), dim3(grid), dim3(64), 0, stream, d_src,
+                       d_src_off, d_src_len, d_dst, d_dst_off, d_dst_cap, d_out_len, n, nullptr, 0, 1, d_dict + dict_len,
+                       t, (const u32x4*)d_table);
     return (int)hipGetLastError();
 }
 

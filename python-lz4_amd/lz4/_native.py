@@ -58,6 +58,9 @@ def _declare(lib) -> None:
         "lz4m_compress_linked_passes": ([], i32),
         "lz4m_pcompress_large_workspace_size": ([i64, i32], C.c_size_t),
         "lz4m_pcompress_large_batch": ([vp, vp, vp, vp, vp, vp, vp, i64, i32, vp, C.c_size_t, vp], i32),
+        "lz4m_pcompress_dict_table_bytes": ([], C.c_size_t),
+        "lz4m_pcompress_dict_prepare": ([vp, i64, vp, C.c_size_t, vp], i32),
+        "lz4m_pcompress_dict_batch": ([vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, i64, vp], i32),
         "lz4m_compress_linked_batch": ([vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, vp, C.c_size_t, vp], i32),
         "lz4m_compress_hc_workspace_size": ([i64, i32], C.c_size_t),
         "lz4m_compress_hc_batch": ([vp, vp, vp, vp, vp, vp, vp, i64, i32, vp, C.c_size_t, vp], i32),
@@ -257,6 +260,29 @@ def launch_compress_dict(src, src_off, src_len, dict_len, dst, dst_off, dst_cap,
     rc = getattr(lib(), name)(ptr(src), ptr(src_off), ptr(src_len), ptr(dict_len), ptr(dst), ptr(dst_off),
                               ptr(dst_cap), ptr(out_len), n, accel, stream_ptr(stream))
     check(rc, name)
+
+
+def pcompress_dict_prepare(dict_buf: torch.Tensor, stream=None) -> torch.Tensor:
+    """The 8 KiB table of a device-resident dictionary (its last 64 KiB count)
+    for launch_pcompress_dict (lz4m_pcompress_dict_prepare), stream-ordered."""
+    L = lib()
+    table = _empty_on(stream, L.lz4m_pcompress_dict_table_bytes(), dict_buf.device)
+    n = dict_buf.numel()
+    check(L.lz4m_pcompress_dict_prepare(ptr(dict_buf) if n else None, n, ptr(table), table.numel(), stream_ptr(stream)),
+          "lz4m_pcompress_dict_prepare")
+    return table
+
+
+def launch_pcompress_dict(src, src_off, src_len, dict_buf, table, dst, dst_off, dst_cap, out_len, n,
+                          stream=None) -> None:
+    """PARSE_PARALLEL with ``dict_buf`` (uint8, device) as the one dictionary
+    of all n blocks and ``table`` = pcompress_dict_prepare(dict_buf)
+    (lz4m_pcompress_dict_batch); the blocks decode with that dictionary."""
+    nd = dict_buf.numel()
+    rc = lib().lz4m_pcompress_dict_batch(ptr(src), ptr(src_off), ptr(src_len), ptr(dict_buf) if nd else None, nd,
+                                         ptr(table), ptr(dst), ptr(dst_off), ptr(dst_cap), ptr(out_len), n,
+                                         stream_ptr(stream))
+    check(rc, "lz4m_pcompress_dict_batch")
 
 
 def launch_compress_hc(src, src_off, src_len, dst, dst_off, dst_cap, out_len, n, level: int = 9, stream=None,

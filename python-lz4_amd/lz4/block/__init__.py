@@ -8,6 +8,8 @@ from ._block import (  # noqa: F401  batched / device-resident extensions
     decompress_host,
     compact,
     xxh32_batch,
+    prepare_dict,
+    PreparedDict,
     HC_LEVEL_MIN,
     HC_LEVEL_DEFAULT,
     HC_LEVEL_OPT_MIN,

@@ -348,6 +348,52 @@ def _stage_out(lay: _Layout, h: torch.Tensor, d: torch.Tensor, n: int):
     return hn[lay.result:lay.result + 4 * n].view(np.int32).tolist(), hn[lay.out:lay.total]
 
 
+_DICT_WINDOW = 65536   # the bytes of a dictionary an LZ4 block can reach
+
+
+class PreparedDict:
+    """A dictionary made ready for the parallel parse (``prepare_dict``):
+    ``tail``, the device copy of its last 64 KiB; ``dict_len``, its full
+    length; ``table``, the 8 KiB hash table of the tail
+    (lz4m_pcompress_dict_prepare).  Hashed once, used by any number of
+    ``compress_batch(dict_buf=)`` / ``compress_many(dict=)`` calls; the blocks
+    decode with the dictionary's bytes (``decompress_many(dict=)``,
+    ``decompress_batch(dict_buf=prepared.tail)``)."""
+
+    __slots__ = ("tail", "dict_len", "table")
+
+    def __init__(self, tail: torch.Tensor, dict_len: int, table: torch.Tensor):
+        self.tail, self.dict_len, self.table = tail, dict_len, table
+
+
+def _prepare_dict(d, stream=None, copy: bool = True) -> PreparedDict:
+    if isinstance(d, PreparedDict):
+        return d
+    if isinstance(d, torch.Tensor):
+        if d.dtype != torch.uint8 or d.dim() != 1 or not d.is_cuda:
+            raise ValueError("a dictionary tensor must be a one-dimensional uint8 device tensor")
+        tail = d[max(d.numel() - _DICT_WINDOW, 0):]
+        if copy or not tail.is_contiguous():
+            with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(d.device)):
+                tail = tail.clone()
+        full = d.numel()
+    else:
+        dv = _buffer(d, "dict")
+        full = dv.nbytes
+        tail = N.to_device(dv[max(full - _DICT_WINDOW, 0):], N.device())
+        if stream is not None:   # the upload ran on the current stream
+            stream.wait_stream(torch.cuda.current_stream(tail.device))
+    return PreparedDict(tail, full, N.pcompress_dict_prepare(tail, stream))
+
+
+def prepare_dict(dict, stream=None) -> PreparedDict:
+    """Upload (a host buffer) or copy (a uint8 device tensor) the last 64 KiB
+    of ``dict`` and hash them, once, for ``compress_batch(table=PARSE_PARALLEL,
+    dict_buf=)`` and ``compress_many(dict=, table=PARSE_PARALLEL)``.  Stream-
+    ordered on ``stream`` (default: the current one)."""
+    return _prepare_dict(dict, stream)
+
+
 def compress_many(blocks, accel: int = 1, store_size: bool = True, as_bytearray: bool = False,
                   table: int = N.TABLE_U32_HASH5, dict=None, dict_prefix: bool = False,
                   mode: str = "default", compression: int = 9):
@@ -364,9 +410,19 @@ def compress_many(blocks, accel: int = 1, store_size: bool = True, as_bytearray:
     With ``dict`` of any length (lz4m_compress_hc_dict_batch) matches may
     reach into the dictionary's last 64 KiB, and the result decodes with
     ``lz4.block.decompress(comp, dict=dict)``; an empty ``dict`` gives the
-    bytes of no ``dict``."""
+    bytes of no ``dict``.
+    ``dict`` with ``table=PARSE_PARALLEL`` (mode "default", no
+    ``dict_prefix``): the parallel parse with the dictionary as every block's
+    history (lz4m_pcompress_dict_batch): blocks up to 64 KiB, valid blocks
+    that decode with ``dict=dict``, not byte-identical to the exact parse.
+    The dictionary is uploaded and hashed once per call -- not staged with
+    every block -- or not at all when ``dict`` is a ``PreparedDict``
+    (``prepare_dict``), which only this combination accepts."""
     hc = _hc_mode(mode)
     compression = _c_int(compression, "compression")
+    shared = dict is not None and not hc and not dict_prefix and table == N.PARSE_PARALLEL
+    if isinstance(dict, PreparedDict) and not shared:
+        raise ValueError("a PreparedDict is only valid with table=PARSE_PARALLEL, mode='default' and no dict_prefix")
     views = [_buffer(b) for b in blocks]
     dev = N.device()
     n = len(views)
@@ -375,7 +431,7 @@ def compress_many(blocks, accel: int = 1, store_size: bool = True, as_bytearray:
     lens = [v.nbytes for v in views]
     caps = [max(N.compress_bound(L), 1) for L in lens]
     d_off = _excl_offsets(caps)
-    if dict is None:
+    if dict is None or shared:
         offs = _excl_offsets(lens)
         payload = views
     else:
@@ -387,8 +443,11 @@ def compress_many(blocks, accel: int = 1, store_size: bool = True, as_bytearray:
         payload = [x for v in views for x in (tail, v)]
     lay, h, d = _stage_in(dev, payload, offs, lens, d_off, caps)
     d_src, src_off, src_len, d_dst, dst_off, dst_cap, out_len = _dev_views(lay, d, n)
-    dict_len = None if dict is None else torch.full((n,), dv.nbytes, dtype=torch.int32, device=dev)
-    if hc:
+    dict_len = None if dict is None or shared else torch.full((n,), dv.nbytes, dtype=torch.int32, device=dev)
+    if shared:
+        pd = _prepare_dict(dict)
+        N.launch_pcompress_dict(d_src, src_off, src_len, pd.tail, pd.table, d_dst, dst_off, dst_cap, out_len, n)
+    elif hc:
         N.launch_compress_hc(d_src, src_off, src_len, d_dst, dst_off, dst_cap, out_len, n, compression,
                              max_len=max(lens), dict_len=dict_len)
     elif dict is None:
@@ -479,7 +538,8 @@ def decompress_many(blocks, uncompressed_size=-1, dict=None, as_bytearray: bool 
 def compress_batch(src: torch.Tensor, src_off: torch.Tensor, src_len: torch.Tensor, *,
                    table: str | int = "block", acceleration: int = 1, dst: torch.Tensor | None = None,
                    dst_off: torch.Tensor | None = None, dst_cap: torch.Tensor | None = None, stream=None,
-                   mode: str = "default", compression: int = 9, dict_len: torch.Tensor | None = None):
+                   mode: str = "default", compression: int = 9, dict_len: torch.Tensor | None = None,
+                   dict_buf: "PreparedDict | torch.Tensor | None" = None):
     """Compress n device-resident blocks in one stream-ordered launch.
 
     ``src`` uint8 (HBM), ``src_off`` int64[n], ``src_len`` int32[n].
@@ -501,9 +561,24 @@ def compress_batch(src: torch.Tensor, src_off: torch.Tensor, src_len: torch.Tens
     65536) bytes lie immediately before it in ``src``; matches may reach into
     them, and the block decodes with those bytes as its dictionary.
     dict_len[i] <= 0: no dictionary.
+
+    ``dict_buf`` (``table=PARSE_PARALLEL`` only, lz4m_pcompress_dict_batch):
+    the one dictionary of all blocks, the counterpart of
+    ``decompress_batch(dict_buf=)``: a ``PreparedDict`` (``prepare_dict``), or
+    a uint8 device tensor, which is hashed on the spot on the call's stream
+    (neither is copied per block).  Matches may reach into its last 64 KiB;
+    the blocks (up to 64 KiB each) decode with it as their dictionary.  Below
+    4 bytes it changes nothing.
     """
     hc = _hc_mode(mode)
     compression = _c_int(compression, "compression")
+    if dict_buf is not None:
+        if hc:
+            raise ValueError("dict_buf is not valid with mode='high_compression' (use dict_len)")
+        if dict_len is not None:
+            raise ValueError("dict_buf (one shared dictionary) and dict_len (one per block) exclude each other")
+        if table != N.PARSE_PARALLEL:
+            raise ValueError("dict_buf is only valid with table=PARSE_PARALLEL")
     if dict_len is not None and not hc:
         raise ValueError("dict_len is only valid with mode='high_compression'")
     tab = {"block": N.TABLE_U32_HASH5, "default": N.TABLE_AUTO, "u16": N.TABLE_U16_HASH4}.get(table, table)
@@ -521,6 +596,11 @@ def compress_batch(src: torch.Tensor, src_off: torch.Tensor, src_len: torch.Tens
         if n:
             N.launch_compress_hc(src, src_off, src_len, dst, dst_off, dst_cap, out_len, n, compression, stream,
                                  dict_len=None if dict_len is None else dict_len.to(torch.int32))
+    elif dict_buf is not None:
+        if n:
+            pd = _prepare_dict(dict_buf, stream, copy=False)
+            N.launch_pcompress_dict(src, src_off, src_len, pd.tail, pd.table, dst, dst_off, dst_cap, out_len, n,
+                                    stream)
     else:
         N.launch_compress(src, src_off, src_len, dst, dst_off, dst_cap, out_len, n, int(tab), int(acceleration),
                           stream)
