@@ -15,6 +15,8 @@ pytestmark = pytest.mark.gpu
 from lz4 import _native as N
 from lz4 import _synth
 
+from layout_support import malformed_cases, _literal_block, _long_sequence_blocks, _offset0_block
+
 
 def _pack(blocks):
     offs, lens, total = [], [], 0
@@ -127,24 +129,6 @@ def test_compress_large_block_u32(gpu, oracle, corpus):
     big = b"".join(blocks[:20])   # 1.25 MiB, byU32 with distance check
     got = gpu_compress([big], N.TABLE_U32_HASH5, gpu)[0]
     assert got == oracle.compress(big, N.TABLE_U32_HASH5)
-
-
-def malformed_cases(oracle, blocks, count=3000, seed=1234):
-    """Mutated and truncated blocks with capacities around the true size."""
-    rng = random.Random(seed)
-    cases, caps = [], []
-    for _ in range(count):
-        b = blocks[rng.randrange(len(blocks))]
-        n = rng.choice([20, 64, 100, 300, 2000, 65536])
-        off = rng.randrange(0, 65536 - n + 1)
-        c = bytearray(oracle.compress(b[off:off + n]))
-        for _ in range(rng.randrange(4)):
-            c[rng.randrange(len(c))] = rng.randrange(256)
-        if rng.random() < 0.2:
-            c = c[:rng.randrange(len(c) + 1)]
-        cases.append(bytes(c))
-        caps.append(rng.choice([n, n, n - 1, n + 1, n + 100, max(0, n - 20), 70, 0]))
-    return cases, caps
 
 
 @pytest.mark.parametrize("decoder", DECODERS)
@@ -450,14 +434,6 @@ def test_decompress_kinds_and_sizes(gpu, oracle, kind, block, decoder):
         assert st == len(b) and out == b
 
 
-def _literal_block(payload, tok=0xF0, tail=b""):
-    """One sequence whose literal is `payload` (length bytes as the format
-    writes them), then `tail`: a whole-literal block when tail is empty."""
-    n = len(payload) - 15
-    run = b"\xff" * (n // 255) + bytes([n % 255])
-    return bytes([tok]) + run + payload + tail
-
-
 @pytest.mark.parametrize("decoder", DECODERS)
 def test_decompress_whole_literal_blocks(gpu, oracle, decoder):
     """Incompressible blocks -- one literal running exactly to the block's end,
@@ -502,37 +478,6 @@ def test_decompress_whole_literal_blocks(gpu, oracle, decoder):
         assert s == want[0], (i, s, want[0], caps[i])
         if s >= 0:
             assert out == want[1], i
-
-
-def _long_sequence_blocks(n, seed):
-    """Blocks whose sequences do not fit the row decoder's history or its
-    length bytes: literals of 200-700 bytes (compressed length >= 255, the
-    parse's escape), matches of 300-6000 bytes at offsets from 1 to ~5 000
-    (overlapping periodic copies and far ones), zero runs."""
-    rng = np.random.default_rng(seed)
-    out = []
-    for _ in range(n):
-        b = bytearray()
-        while len(b) < 65536:
-            k = int(rng.integers(0, 5))
-            if k == 0:
-                b += rng.integers(0, 256, size=int(rng.choice([1, 14, 15, 16, 200, 270, 600, 700])), dtype=np.uint8).tobytes()
-            elif k == 1 and len(b) > 16:
-                per = int(rng.choice([1, 2, 3, 7, 15, 16, 17, 40, 300, 900, 1300]))
-                per = min(per, len(b))
-                ml = int(rng.choice([300, 1300, 2000, 6000]))
-                src = bytes(b[-per:])
-                b += (src * (ml // per + 1))[:ml]
-            elif k == 2 and len(b) > 5000:
-                off = int(rng.integers(1300, 5000))
-                ml = int(rng.integers(300, 3000))
-                st = len(b) - off
-                for i in range(ml):
-                    b.append(b[st + i])
-            else:
-                b += bytes(int(rng.integers(64, 4096)))
-        out.append(bytes(b[:65536]))
-    return out
 
 
 @pytest.mark.parametrize("decoder", DECODERS)
@@ -581,13 +526,6 @@ def test_decompress_unaligned_input_base(gpu, oracle, corpus, shift):
         assert s == want[0], (i, s, want[0])
         if s > 0:
             assert host[d_off[i]:d_off[i] + s].tobytes() == want[1], i
-
-
-def _offset0_block(lit, ml):
-    """A block whose one match has offset 0 (LZ4_decompress_safe v1.9.4 zero-fills
-    it) followed by 5 final literals."""
-    seq = bytes([(len(lit) << 4) | (ml - 4)]) + lit + b"\x00\x00"
-    return seq + bytes([5 << 4]) + b"tail!"
 
 
 @pytest.mark.parametrize("decoder", ["auto", "hist"])
