@@ -191,7 +191,7 @@ int lz4m_pcompress_dict_batch(const uint8_t* d_src, const int64_t* d_src_off, co
  * section 9, which tests/hc_model/hc_model.c restates on the CPU byte for byte.
  * `level` as in lz4hc.c: below 1 means 9; 1-2 search 2 chain candidates per
  * position, 3 -> 4, 4 -> 8, ... 9 -> 256; levels 10-12 and above search as 9
- * (the reference's optimal parser is not built).  Blocks of any length up to
+ * (lz4m_compress_opt_batch is the higher-ratio parse).  Blocks of any length up to
  * LZ4_MAX_INPUT_SIZE; offsets are limited to 65535 (LZ4_DISTANCE_MAX).
  * d_out_len[i] = compressed size, or 0 when this parse's block does not fit
  * in d_dst_cap[i] bytes (an exact fit is accepted; nothing is written past
@@ -210,7 +210,40 @@ int lz4m_compress_hc_batch(const uint8_t* d_src, const int64_t* d_src_off, const
                            lz4m_stream_t stream);
 
 /*
- * The same compressor for blocks with history: what
+ * Batched lz4.block.compress(mode="optimal", compression=level): a price-based
+ * optimal parse on the device (lz4m_opt.hip).  The longest match of every
+ * position (lz4m_compress_hc_batch's tables and level table: `level` below 1
+ * means 9, 3 -> 4 chain candidates ... 9 -> 256, above 9 as 9) feeds a
+ * backward pass over exact prices that chooses, per position, a literal or
+ * one of the match's 64 longest lengths.  Every result is a valid LZ4 block,
+ * NOT byte-identical to lz4hc.c: the parse is the serial algorithm of
+ * DESIGN.md section 9.7, which tests/hc_model/opt_model.c restates on the CPU
+ * byte for byte.  At level 9 it is within 1 % of LZ4_compress_HC(level 12) on
+ * compressible data and 2.2-2.4 % smaller than lz4m_compress_hc_batch on text
+ * and source.  No history (no dictionary, no linked blocks).
+ * d_out_len[i] = compressed size, or 0 when the block does not fit in
+ * d_dst_cap[i] bytes (an exact fit is accepted; a block that does not fit
+ * writes nothing).  d_work: lz4m_compress_opt_workspace_size(n, max_len)
+ * bytes of device scratch, 4-byte aligned, not shared with a concurrently
+ * running call: 10 bytes per position of a block (its match, price and chain
+ * entry), (max_len + 64 rounded down to a multiple of 64) positions for each
+ * of min(n, 2560) wavefronts -- 640 KiB per wavefront and at most 1.6 GiB for
+ * 64 KiB blocks, whatever n is.  max_len is the longest block of the batch;
+ * a longer block than the workspace was sized for reports 0.  More than the
+ * asked-for bytes changes nothing in the output.  Two launches (blocks up to
+ * 64 KiB, longer blocks), stream-ordered, no host synchronisation, no
+ * allocation.  LZ4M_EINVAL, before any launch: n < 0, or a missing, misaligned
+ * or short (below lz4m_compress_opt_workspace_size(n, 0)) workspace; n == 0
+ * returns 0.
+ */
+size_t lz4m_compress_opt_workspace_size(int64_t n, int32_t max_len);
+int lz4m_compress_opt_batch(const uint8_t* d_src, const int64_t* d_src_off, const int32_t* d_src_len,
+                            uint8_t* d_dst, const int64_t* d_dst_off, const int32_t* d_dst_cap,
+                            int32_t* d_out_len, int64_t n, int level, void* d_work, size_t work_bytes,
+                            lz4m_stream_t stream);
+
+/*
+ * The HC compressor (lz4m_compress_hc_batch) for blocks with history: what
  * lz4.block.compress(mode="high_compression", dict=D) computes with
  * LZ4_loadDictHC + LZ4_compress_HC_continue (_block.c:112-119), and what a
  * linked LZ4 frame's HC block sees of the input before it.  Layout as in

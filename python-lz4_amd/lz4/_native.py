@@ -64,6 +64,8 @@ def _declare(lib) -> None:
         "lz4m_compress_linked_batch": ([vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, vp, C.c_size_t, vp], i32),
         "lz4m_compress_hc_workspace_size": ([i64, i32], C.c_size_t),
         "lz4m_compress_hc_batch": ([vp, vp, vp, vp, vp, vp, vp, i64, i32, vp, C.c_size_t, vp], i32),
+        "lz4m_compress_opt_workspace_size": ([i64, i32], C.c_size_t),
+        "lz4m_compress_opt_batch": ([vp, vp, vp, vp, vp, vp, vp, i64, i32, vp, C.c_size_t, vp], i32),
         "lz4m_compress_hc_dict_workspace_size": ([i64, i32], C.c_size_t),
         "lz4m_compress_hc_dict_batch": ([vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, vp, C.c_size_t, vp], i32),
         "lz4m_xxh32_batch": ([vp, vp, vp, u32, vp, i64, vp], i32),
@@ -303,6 +305,27 @@ def launch_compress_hc(src, src_off, src_len, dst, dst_off, dst_cap, out_len, n,
     rc = getattr(lib(), name)(p(src), p(src_off), p(src_len), *hist, p(dst), p(dst_off), p(dst_cap), p(out_len), n,
                               level, ptr(work), 0 if work is None else work.numel(), stream_ptr(stream))
     check(rc, name)
+
+
+def launch_compress_opt(src, src_off, src_len, dst, dst_off, dst_cap, out_len, n, level: int = 9, stream=None,
+                        max_len: int | None = None) -> None:
+    """Batched optimal-parse compression (lz4m_compress_opt_batch): valid
+    blocks within 1 % of LZ4_compress_HC(12) at level 9, not byte-identical to
+    it.  ``max_len`` is the longest block; None reads it back from ``src_len``
+    (one host synchronisation).  The workspace (10 bytes per position for each
+    of min(n, 2560) wavefronts: 1.6 GiB at most for 64 KiB blocks) is
+    allocated per call on the stream that uses it, from torch's caching
+    allocator."""
+    if n <= 0:
+        check(lib().lz4m_compress_opt_batch(None, None, None, None, None, None, None, n, level, None, 0,
+                                            stream_ptr(stream)), "lz4m_compress_opt_batch")
+        return
+    if max_len is None:
+        max_len = max(int(src_len.max().item()), 0)
+    work = _empty_on(stream, lib().lz4m_compress_opt_workspace_size(n, max_len), src.device)
+    rc = lib().lz4m_compress_opt_batch(ptr(src), ptr(src_off), ptr(src_len), ptr(dst), ptr(dst_off), ptr(dst_cap),
+                                       ptr(out_len), n, level, ptr(work), work.numel(), stream_ptr(stream))
+    check(rc, "lz4m_compress_opt_batch")
 
 
 def launch_compress_linked(src, src_off, src_len, link, dst, dst_off, dst_cap, out_len, n, accel,

@@ -62,26 +62,37 @@ def _buffer(obj, name: str = "source") -> memoryview:
 
 
 def _mode_accel(mode, acceleration: int) -> int | None:
-    """The acceleration of the non-HC modes; None for 'high_compression'."""
+    """The acceleration of the non-HC modes; None for 'high_compression' and 'optimal'."""
     if not isinstance(mode, str):
         raise TypeError(f"compress() argument 'mode' must be str, not {type(mode).__name__}")
     if mode == "default":
         return 1
     if mode == "fast":
         return acceleration
-    if mode == "high_compression":
+    if mode in ("high_compression", "optimal"):
         return None
-    raise ValueError(f"Invalid mode argument: {mode}. Must be one of: standard, fast, high_compression")
+    raise ValueError(f"Invalid mode argument: {mode}. Must be one of: standard, fast, high_compression, optimal")
 
 
 def _hc_mode(mode) -> bool:
     """``mode`` of the batched calls: "default" (the exact compressors, chosen
-    by their own ``table`` / ``accel`` arguments) or "high_compression"."""
+    by their own ``table`` / ``accel`` arguments), "high_compression" or
+    "optimal" (true for both; _opt_mode tells them apart)."""
     if mode == "default":
         return False
-    if mode == "high_compression":
+    if mode in ("high_compression", "optimal"):
         return True
-    raise ValueError(f"Invalid mode argument: {mode}. Must be one of: default, high_compression")
+    raise ValueError(f"Invalid mode argument: {mode}. Must be one of: default, high_compression, optimal")
+
+
+def _opt_mode(mode, dict=None, dict_len=None) -> bool:
+    """True for mode="optimal", which takes no dictionary."""
+    if mode != "optimal":
+        return False
+    if dict is not None or dict_len is not None:
+        raise NotImplementedError("mode='optimal' with a dictionary (dict= / dict_len=) is not built: the optimal "
+                                  "parse has no history; use mode='high_compression' with a dictionary")
+    return True
 
 
 def _cap_and_skip(view: memoryview, uncompressed_size: int):
@@ -141,10 +152,16 @@ def compress(source, mode="default", store_size=True, acceleration=1, compressio
     hash-chain compressor at level ``compression`` (lz4m_compress_hc_batch):
     a valid block near the size of ``LZ4_compress_HC`` at that level, NOT
     byte-identical to it.  Levels below 1 mean 9; levels 10-12 and above
-    search as level 9 (the reference's optimal parser is not built).  HC with
+    search as level 9 (``mode='optimal'`` is the higher-ratio parse).  HC with
     ``dict=`` (``LZ4_loadDictHC``) raises ``NotImplementedError`` from this
     call; ``compress_many(mode='high_compression', dict=D)`` and
     ``compress_batch(dict_len=)`` compress with a dictionary.
+
+    ``mode='optimal'`` (not in the reference's binding) runs the device's
+    price-based optimal parse searching as level ``compression``
+    (lz4m_compress_opt_batch): at level 9 a valid block within 1 % of
+    ``LZ4_compress_HC`` at level 12, NOT byte-identical to it.  ``dict=``
+    raises ``NotImplementedError``: the optimal parse takes no dictionary.
     """
     src = _buffer(source)
     acceleration = _c_int(acceleration, "acceleration")
@@ -158,12 +175,13 @@ def compress(source, mode="default", store_size=True, acceleration=1, compressio
             raise OverflowError("Dictionary too large for LZ4 API")
     accel = _mode_accel(mode, acceleration)
     if accel is None:
+        _opt_mode(mode, dict=d)
         if d is not None:
             raise NotImplementedError(
                 "mode='high_compression' with dict= (LZ4_loadDictHC) is not built on the MI355X codec; "
                 "compress without a dictionary, or use mode='default' or mode='fast' with dict=")
         out = compress_many([src], store_size=bool(store_size), as_bytearray=bool(return_bytearray),
-                            mode="high_compression", compression=compression)[0]
+                            mode=mode, compression=compression)[0]
         if out is None:
             raise LZ4BlockError("Compression failed")
         return out
@@ -411,6 +429,9 @@ def compress_many(blocks, accel: int = 1, store_size: bool = True, as_bytearray:
     reach into the dictionary's last 64 KiB, and the result decodes with
     ``lz4.block.decompress(comp, dict=dict)``; an empty ``dict`` gives the
     bytes of no ``dict``.
+    ``mode="optimal"``: the price-based optimal parse searching as level
+    ``compression`` (lz4m_compress_opt_batch); ``dict`` raises
+    ``NotImplementedError``.
     ``dict`` with ``table=PARSE_PARALLEL`` (mode "default", no
     ``dict_prefix``): the parallel parse with the dictionary as every block's
     history (lz4m_pcompress_dict_batch): blocks up to 64 KiB, valid blocks
@@ -419,6 +440,7 @@ def compress_many(blocks, accel: int = 1, store_size: bool = True, as_bytearray:
     every block -- or not at all when ``dict`` is a ``PreparedDict``
     (``prepare_dict``), which only this combination accepts."""
     hc = _hc_mode(mode)
+    opt = _opt_mode(mode, dict=dict)
     compression = _c_int(compression, "compression")
     shared = dict is not None and not hc and not dict_prefix and table == N.PARSE_PARALLEL
     if isinstance(dict, PreparedDict) and not shared:
@@ -447,6 +469,9 @@ def compress_many(blocks, accel: int = 1, store_size: bool = True, as_bytearray:
     if shared:
         pd = _prepare_dict(dict)
         N.launch_pcompress_dict(d_src, src_off, src_len, pd.tail, pd.table, d_dst, dst_off, dst_cap, out_len, n)
+    elif opt:
+        N.launch_compress_opt(d_src, src_off, src_len, d_dst, dst_off, dst_cap, out_len, n, compression,
+                              max_len=max(lens))
     elif hc:
         N.launch_compress_hc(d_src, src_off, src_len, d_dst, dst_off, dst_cap, out_len, n, compression,
                              max_len=max(lens), dict_len=dict_len)
@@ -554,13 +579,19 @@ def compress_batch(src: torch.Tensor, src_off: torch.Tensor, src_len: torch.Tens
     ``acceleration`` are ignored): valid blocks near the size of
     LZ4_compress_HC at that level, NOT byte-identical to it.  Levels below 1
     mean 9, 3..9 search 4..256 chain candidates per position, levels 10-12
-    and above search as 9 (the reference's optimal parser is not built).  A
+    and above search as 9 (``mode="optimal"`` is the higher-ratio parse).  A
     block that does not fit its slot reports 0; an exact fit is accepted.
     ``dict_len`` int32[n] (this mode only, lz4m_compress_hc_dict_batch):
     block i has a dictionary of dict_len[i] bytes whose last min(dict_len[i],
     65536) bytes lie immediately before it in ``src``; matches may reach into
     them, and the block decodes with those bytes as its dictionary.
     dict_len[i] <= 0: no dictionary.
+
+    ``mode="optimal"``: the price-based optimal parse searching as level
+    ``compression`` (lz4m_compress_opt_batch): at level 9 within 1 % of
+    LZ4_compress_HC(12), NOT byte-identical.  Its workspace grows with the
+    longest block, so this mode reads ``src_len.max()`` back: one host
+    synchronisation.  ``dict_len`` / ``dict_buf`` raise NotImplementedError.
 
     ``dict_buf`` (``table=PARSE_PARALLEL`` only, lz4m_pcompress_dict_batch):
     the one dictionary of all blocks, the counterpart of
@@ -571,6 +602,7 @@ def compress_batch(src: torch.Tensor, src_off: torch.Tensor, src_len: torch.Tens
     4 bytes it changes nothing.
     """
     hc = _hc_mode(mode)
+    opt = _opt_mode(mode, dict=dict_buf, dict_len=dict_len)
     compression = _c_int(compression, "compression")
     if dict_buf is not None:
         if hc:
@@ -592,7 +624,10 @@ def compress_batch(src: torch.Tensor, src_off: torch.Tensor, src_len: torch.Tens
         total = int((dst_off[-1] + dst_cap[-1]).item()) if n else 1
         dst = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
     out_len = torch.empty(n, dtype=torch.int32, device=dev)
-    if hc:
+    if opt:
+        if n:
+            N.launch_compress_opt(src, src_off, src_len, dst, dst_off, dst_cap, out_len, n, compression, stream)
+    elif hc:
         if n:
             N.launch_compress_hc(src, src_off, src_len, dst, dst_off, dst_cap, out_len, n, compression, stream,
                                  dict_len=None if dict_len is None else dict_len.to(torch.int32))

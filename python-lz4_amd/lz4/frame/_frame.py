@@ -214,6 +214,10 @@ def compress_device(d_src: torch.Tensor, n: int | None = None, *, compression_le
     byte-identical).  A linked frame's blocks, each with the 64 KiB of input
     before it as history, are compressed in one launch
     (lz4m_compress_hc_dict_batch).
+    parse="optimal" with compression_level >= 3: the price-based optimal parse
+    searching as that level (lz4m_compress_opt_batch; at level 9 within 1 % of
+    the reference's level 12, not byte-identical).  Independent blocks only:
+    with block_linked=True it raises NotImplementedError.
 
     The content checksum (one serial XXH32 stream over all of d_src) runs on
     a host core beside the block compression, over pipelined PCIe copies of
@@ -235,14 +239,26 @@ def _host_wait(stream) -> None:
 def _parse_level(parse, compression_level):
     """(level, acceleration) of a device compression call, or its argument error."""
     level = int(compression_level)
-    if parse not in ("exact", "parallel", "hc"):
-        raise ValueError("parse must be 'exact', 'parallel' or 'hc'")
-    if parse == "hc":
+    if parse not in ("exact", "parallel", "hc", "optimal"):
+        raise ValueError("parse must be 'exact', 'parallel', 'hc' or 'optimal'")
+    if parse in ("hc", "optimal"):
         if level < 3:
-            raise ValueError("parse='hc' needs compression_level >= 3 (levels 0-2 are the fast compressor)")
+            raise ValueError(f"parse='{parse}' needs compression_level >= 3 (levels 0-2 are the fast compressor)")
     elif level >= 3:
         raise NotImplementedError("LZ4 HC compression levels (>= 3) are outside the MI355X codec's scope")
     return level, (-level + 1 if level < 0 else 1)             # lz4frame.c:855
+
+
+class LinkedOptimalError(NotImplementedError, ValueError):
+    """parse="optimal" asked for linked blocks: a combination that is not
+    built (NotImplementedError) and, until it is, a bad value of ``parse`` for
+    a linked frame (ValueError, what an unknown parse raises)."""
+
+
+def _no_linked_optimal(parse, block_linked) -> None:
+    if parse == "optimal" and block_linked:
+        raise LinkedOptimalError("parse='optimal' has no history: block_linked=True is not built "
+                                 "(pass block_linked=False, or parse='hc' for linked blocks)")
 
 
 def _compress_frame(d_src, n=None, *, compression_level=0, block_size=0, content_checksum=False,
@@ -254,6 +270,7 @@ def _compress_frame(d_src, n=None, *, compression_level=0, block_size=0, content
     it is stored raw (None when the input is empty)."""
     n = d_src.numel() if n is None else int(n)
     level, accel = _parse_level(parse, compression_level)
+    _no_linked_optimal(parse, block_linked)
     bsid = _optimal_bsid(int(block_size), n)
     if bsid == 0:
         bsid = BLOCKSIZE_MAX64KB                               # LZ4F_BLOCKSIZEID_DEFAULT
@@ -293,6 +310,9 @@ def _compress_frame(d_src, n=None, *, compression_level=0, block_size=0, content
             hist = raw_off.clamp(max=65536).to(torch.int32) if linked else None
             N.launch_compress_hc(d_src, raw_off, raw_len, cmp, cmp_off, cap, cmp_len, nb, level, stream,
                                  max_len=bsize, dict_len=hist)
+        elif parse == "optimal":
+            N.launch_compress_opt(d_src, raw_off, raw_len, cmp, cmp_off, cap, cmp_len, nb, level, stream,
+                                  max_len=min(bsize, n))
         elif parse == "exact" and linked:   # one stream across the blocks (lz4frame.c:865-871)
             link = torch.ones(nb, dtype=torch.int32, device=dev)
             link[0] = 0
@@ -931,7 +951,9 @@ def compress_batch(src, src_off, src_len, *, compression_level=0, block_size=0, 
     frames[frame_off[i] : frame_off[i] + frame_len[i]] (int64 device tensors;
     the frames lie back to back).  Frame i holds the bytes of
     ``compress_device(input i, same options)`` for parse="exact" and
-    parse="hc"; parse="parallel" gives valid frames of the parallel parse.
+    parse="hc" and parse="optimal" (independent blocks only: block_linked=True
+    raises NotImplementedError); parse="parallel" gives valid frames of the
+    parallel parse.
 
     The blocks of all frames are compressed together: those of linked frames
     (block_linked and an input above one block) as one stream per frame
@@ -941,6 +963,7 @@ def compress_batch(src, src_off, src_len, *, compression_level=0, block_size=0, 
     on the device, four lanes per frame (lz4m_xxh32_batch): a very large frame
     in a batch hashes serially; that is what the single-frame calls are for."""
     level, accel = _parse_level(parse, compression_level)
+    _no_linked_optimal(parse, block_linked)
     req = max(-1, min(int(block_size), 8))   # beyond 7 it is no block size whatever the input's length
     with _on(stream):
         off, ln, src_total = _spans(src, src_off, src_len, "src")
@@ -1002,6 +1025,10 @@ def _compress_blocks(src, P, cmp, cmp_off, cmp_len, parse, level, accel, bsid, l
         big = bsid[P["owner"]] > BLOCKSIZE_MAX64KB
         _launch_subset(~big, arrays, cmp_len, small)
         _launch_subset(big, arrays, cmp_len, large)
+        return
+    if parse == "optimal":                                     # independent blocks only
+        N.launch_compress_opt(src, P["raw_off"], P["raw_len"], cmp, cmp_off, P["cap"], cmp_len, nb, level,
+                              max_len=max_block)
         return
     in_linked = linked[P["owner"]] != 0 if n_linked else None
     if parse == "hc":
