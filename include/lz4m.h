@@ -252,7 +252,7 @@ int lz4m_compress_opt_batch(const uint8_t* d_src, const int64_t* d_src_off, cons
  * stored immediately before block i in d_src.  Matches may start in the
  * prefix (offsets up to 65535); the result decodes with
  * LZ4_decompress_safe_usingDict over that prefix.  The parse is DESIGN.md
- * section 9.5 (tests/hc_model/hc_model_prefix.c), NOT byte-identical to
+ * section 9.5 (tests/hc_model/hc_model.c), NOT byte-identical to
  * lz4hc.c.  d_dict_len[i] <= 0: no prefix, the bytes of
  * lz4m_compress_hc_batch.  Three launches: the blocks whose prefix + length
  * is at most 65536 bytes, those up to 131072 (a linked frame's 64 KiB blocks),

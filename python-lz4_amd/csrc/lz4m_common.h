@@ -345,85 +345,4 @@ __device__ __forceinline__ void wave_copy_wild(uint8_t* d, const uint8_t* s, int
     }
 }
 
-// ------------------------------------------- hash-chain (HC, optimal) parses
-// One step of hash-chain insertion takes 64 consecutive positions, lane l the
-// l-th (act: it is inserted, h: its hash of BITS bits).  The lanes that share
-// a hash are found by ballots over the hash bits (no atomics, no reliance on
-// the order in which one instruction's lanes reach the LDS): `below` / `above`
-// are the active lanes under / over this one with its hash.  A position chains
-// to the highest lane of `below`, else to the table's entry; the lane with no
-// `above` writes the table.
-template <int BITS>
-__device__ __forceinline__ void hash_links(bool act, uint32_t h, uint32_t lane, uint64_t& below, uint64_t& above) {
-    uint64_t same = __ballot(act);
-#pragma unroll
-    for (int b = 0; b < BITS; ++b) {
-        const bool bit = (h >> b) & 1u;
-        const uint64_t B = __ballot(bit);
-        same &= bit ? B : ~B;
-    }
-    below = same & ((1ull << lane) - 1ull);
-    above = same & ~((2ull << lane) - 1ull);
-}
-
-// accesses of one lane that another lane of the wave made or will make:
-// relaxed atomics at wavefront scope (plain loads and stores in the ISA),
-// ordered by hc_fence
-template <typename T>
-__device__ __forceinline__ uint32_t hc_ld(const T* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-}
-template <typename T>
-__device__ __forceinline__ void hc_st(T* p, uint32_t v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-}
-__device__ __forceinline__ void hc_fence() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); }
-
-// equal leading bytes of a[..] and b[..], at most lim; reads stay below a + lim and b + lim
-__device__ __forceinline__ int32_t hc_count(const uint8_t* a, const uint8_t* b, int32_t lim) {
-    int32_t k = 0;
-    while (k + 8 <= lim) {
-        const uint64_t x = ld64(a + k) ^ ld64(b + k);
-        if (x) return k + (int32_t)(__builtin_ctzll(x) >> 3);
-        k += 8;
-    }
-    while (k < lim && a[k] == b[k]) ++k;
-    return k;
-}
-
-// the e = ext_len<true>(v) length bytes of v at o
-__device__ __forceinline__ void hc_put_ext(uint8_t* o, int32_t v, int32_t e, uint32_t lane) {
-    if (e == 0) return;
-    for (int32_t k = (int32_t)lane; k < e - 1; k += kWave) o[k] = 255;
-    if (lane == 0) o[e - 1] = (uint8_t)(v - 15 - 255 * (e - 1));
-}
-
-// One sequence at dst + op: ll literals from src + anchor, then (ml > 0) a
-// match of ml bytes at distance off; ml == 0 is the block's last sequence.
-// False (nothing written) if it does not fit in cap.
-__device__ __forceinline__ bool hc_emit(uint8_t* dst, int32_t& op, int32_t cap, const uint8_t* src, int32_t anchor,
-                                        int32_t ll, int32_t off, int32_t ml, uint32_t lane) {
-    const int32_t le = ext_len<true>(ll), me = ml ? ext_len<true>(ml - 4) : 0;
-    const int64_t need = 1 + (int64_t)le + ll + (ml ? 2 + me : 0);
-    if ((int64_t)op + need > (int64_t)cap) return false;
-    uint8_t* o = dst + op;
-    if (lane == 0) {
-        const int32_t mt = ml ? (ml - 4 < 15 ? ml - 4 : 15) : 0;
-        o[0] = (uint8_t)(((ll < 15 ? ll : 15) << 4) | mt);
-    }
-    hc_put_ext(o + 1, ll, le, lane);
-    uint8_t* lit = o + 1 + le;
-    for (int32_t k = (int32_t)lane; k < ll; k += kWave) lit[k] = src[anchor + k];
-    if (ml) {
-        uint8_t* mo = lit + ll;
-        if (lane == 0) {
-            mo[0] = (uint8_t)(off & 0xFF);
-            mo[1] = (uint8_t)(off >> 8);
-        }
-        hc_put_ext(mo + 2, ml - 4, me, lane);
-    }
-    op += (int32_t)need;
-    return true;
-}
-
 }  // namespace lz4m

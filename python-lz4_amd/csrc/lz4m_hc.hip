@@ -38,61 +38,24 @@
 //     comparisons are paid once per 64 candidates.
 // The kernel is bound by the latency of these dependent loads, so what counts
 // is the number of resident waves, which the head table decides (HcCfg).
+// The tables' constants and configurations, the insertion step and the
+// sequence writer are lz4m_chain.h's, shared with lz4m_opt.hip.
 //
 // lz4m_compress_hc_dict_batch (hc_prefix_kernel) is the same parse for a block
 // with up to 64 KiB of history lying before it in memory (a dictionary's tail,
 // or the input before a linked frame's block): DESIGN.md section 9.5,
-// tests/hc_model/hc_model_prefix.c.  Positions then count from the start of
+// hc_model_compress_prefix there.  Positions then count from the start of
 // that prefix, which is inserted before the first search; the per-block body
 // (hc_block) is shared by both entry points.
-#include "lz4m_common.h"
+#include "lz4m_chain.h"
 
 #include "../../include/lz4m.h"
 
 namespace lz4m {
 namespace {
 
-constexpr int kHcHashBits = 13;
-constexpr int kHcHeads = 1 << kHcHashBits;
-constexpr int32_t kHcMaxDist = 65535;    // LZ4_DISTANCE_MAX
-constexpr int32_t kHcSmallMax = 65536;   // longest prefix + block of kHcSmall (u16 heads hold position + 1)
-constexpr int32_t kHcPrefixMax = 65536;  // history bytes used in front of a block
-constexpr int32_t kHcMaxInput = 0x7E000000;
-
-// Three configurations share the parse (M; false / true name the first two).
-// kHcSmall: blocks of up to 64 KiB, prefix included: u16 heads (position + 1
-// <= 65525; 16 KiB of LDS, 10 workgroups per CU of 160 KiB) and a chain
-// indexed by the position.  kHcBig: u32 heads (32 KiB, 5 per CU) and a chain
-// of 2 x 65536 entries indexed by the position mod 131072: positions are
-// inserted up to 127 ahead of a search, and a window of exactly 65536 entries
-// would overwrite that search's oldest candidates.  kHcRebased (prefix kernel
-// only): prefix + block of 65537..131072 bytes, the 64 KiB block of a linked
-// frame; u16 heads again, holding (position mod 65535) + 1, with kHcBig's
-// chain.  Such an entry names the positions d, d + 65535, ... back (d in
-// 1..65535), of which only the first is within LZ4_DISTANCE_MAX; it is the
-// newest position with the hash exactly when its four bytes hash to it (a
-// nearer position with that hash would have replaced the entry), which
-// insertion checks, so the chain is the one kHcBig builds.
-constexpr int kHcSmall = 0, kHcBig = 1, kHcRebased = 2;
+constexpr int32_t kHcPrefixMax = 65536;     // history bytes used in front of a block
 constexpr int32_t kHcRebasedMax = 131072;   // longest prefix + block of kHcRebased
-template <int M>
-struct HcCfg {
-    typedef uint16_t head_t;
-    static constexpr int kWaves = 2560;
-    static constexpr uint32_t kChain = 65536;
-};
-template <>
-struct HcCfg<kHcBig> {
-    typedef uint32_t head_t;
-    static constexpr int kWaves = 1280;
-    static constexpr uint32_t kChain = 131072;
-};
-template <>
-struct HcCfg<kHcRebased> {
-    typedef uint16_t head_t;
-    static constexpr int kWaves = 2560;   // as many of them as the caller's workspace has slices for
-    static constexpr uint32_t kChain = 131072;
-};
 // both kernels' slices fill the same workspace (they run one after the other)
 constexpr size_t kHcWorkMax = (size_t)HcCfg<false>::kWaves * HcCfg<false>::kChain * sizeof(uint16_t);
 static_assert(kHcWorkMax == (size_t)HcCfg<true>::kWaves * HcCfg<true>::kChain * sizeof(uint16_t), "shared workspace");
@@ -103,11 +66,6 @@ struct HcBlock {
     typedef __attribute__((address_space(3))) typename HcCfg<M>::head_t head_t;
     static constexpr uint32_t kMask = HcCfg<M>::kChain - 1u;
 
-    // kHcRebased: position (< 131072) mod 65535
-    static __device__ __forceinline__ uint32_t rebased(uint32_t p) {
-        return p >= 131070u ? p - 131070u : (p >= 65535u ? p - 65535u : p);
-    }
-
     head_t* head;
     uint16_t* chain;
     const uint8_t* src;
@@ -117,34 +75,11 @@ struct HcBlock {
     int32_t attempts;
     uint32_t lane;
 
-    // Insert 64 positions per step until position q is in.  Lane l's position
-    // chains to the nearest earlier lane of the step with the same hash, else
-    // to the table's entry; the last lane of each hash writes the table.
+    // Insert 64 positions per step (hc_insert_step) until position q is in.
     __device__ __forceinline__ void insert_through(int32_t q) {
         while (inserted <= q) {
-            const int32_t base = inserted;
-            const int32_t end = base + kWave < ilimit ? base + kWave : ilimit;
-            const int32_t p = base + (int32_t)lane;
-            const bool act = p < end;
-            uint32_t h = 0;
-            if (act) h = hash4<kHcHashBits>(ld32(src + p));
-            uint64_t below, above;
-            hash_links<kHcHashBits>(act, h, lane, below, above);
-            if (act) {
-                uint32_t prev = below ? (uint32_t)base + (63u - (uint32_t)__builtin_clzll(below)) + 1u
-                                      : hc_ld(head + h);
-                if (M == kHcRebased && !below && prev) {
-                    const uint32_t r = rebased((uint32_t)p), e = prev - 1u;
-                    const uint32_t back = r > e ? r - e : r + 65535u - e;   // 1..65535
-                    prev = back <= (uint32_t)p && hash4<kHcHashBits>(ld32(src + p - (int32_t)back)) == h
-                               ? (uint32_t)p + 1u - back
-                               : 0u;
-                }
-                const uint32_t d = prev ? (uint32_t)p + 1u - prev : 0u;
-                hc_st(chain + ((uint32_t)p & kMask), d > (uint32_t)kHcMaxDist ? 0u : d);
-                if (above == 0) hc_st(head + h, M == kHcRebased ? rebased((uint32_t)p) + 1u : (uint32_t)p + 1u);
-            }
-            hc_fence();
+            const int32_t end = inserted + kWave < ilimit ? inserted + kWave : ilimit;
+            hc_insert_step<M == kHcRebased, kMask>(head, chain, src, inserted, end, lane);
             inserted = end;
         }
     }
@@ -375,14 +310,6 @@ __global__ __launch_bounds__(64) void hc_prefix_kernel(const uint8_t* __restrict
                                                        int32_t attempts, uint16_t* __restrict__ work) {
     hc_grid<M, true>(src_base, src_off, src_len, dict_len, dst_base, dst_off, dst_cap, out_len, nblocks, attempts,
                      work);
-}
-
-// lz4hc.c level table: levels below 1 mean 9; 1-2 -> 2 attempts, 3 -> 4, ...
-// 9 -> 256; levels 10-12 search as 9 here (lz4m_opt.hip is the higher-ratio parse)
-int32_t hc_attempts(int level) {
-    if (level < 1) level = 9;
-    if (level > 9) level = 9;
-    return level < 3 ? 2 : 1 << (level - 1);
 }
 
 }  // namespace

@@ -7,7 +7,7 @@
 // section 9.7 and restated on the CPU by tests/hc_model/opt_model.c; these
 // kernels produce that model's bytes:
 //   - section 9.1's tables (13-bit hash, chain of distances <= 65535) and
-//     level table (`attempts`);
+//     level table (`attempts`): lz4m_chain.h, shared with lz4m_hc.hip;
 //   - L[q], O[q]: the longest forward match among the first `attempts` chain
 //     candidates of q (q <= n - 12), at most min(n - 5 - q, 65535) bytes, the
 //     nearest among equals;
@@ -21,7 +21,7 @@
 // Mapping: one wavefront per block, a persistent grid striding over the batch,
 // the block's state in the wave's slice of the caller's workspace (10 bytes
 // per position: u32 L|O<<16, u32 cost, u16 chain).  Four phases per block:
-//   insert  64 positions per step, linked by ballots (hash_links); the head
+//   insert  64 positions per step, linked by ballots (hc_insert_step); the head
 //           table is the workgroup's LDS.  chain[q] is then the distance to
 //           the newest earlier position with q's hash;
 //   match   64 consecutive positions per step, each lane walking its own chain
@@ -42,38 +42,22 @@
 //   emit    forwards over the choices, 64 positions per look.
 // No phase reads workspace bytes the block did not write, so a block's bytes
 // do not depend on the wave that parsed it or on what the workspace held.
-#include "lz4m_common.h"
+#include "lz4m_chain.h"
 
 #include "../../include/lz4m.h"
 
 namespace lz4m {
 namespace {
 
-constexpr int kOptHashBits = 13;
-constexpr int kOptHeads = 1 << kOptHashBits;
-constexpr int32_t kOptMaxDist = 65535;    // LZ4_DISTANCE_MAX
 constexpr int32_t kOptMaxLen = 65535;     // longest match (u16 L)
-constexpr int32_t kOptSmallMax = 65536;   // longest block of the u16-head kernel (heads hold position + 1)
-constexpr int32_t kOptMaxInput = 0x7E000000;
 constexpr int kOptLengths = 64;           // K: lengths priced per position, one per lane
 constexpr int kOptChunk = 32;             // positions per price chunk
 constexpr int kOptRing = 1024;            // costs kept in LDS
 constexpr int32_t kOptFar = 512 + kOptLengths - 1;   // L from which all 64 costs lie >= 512 positions ahead
 constexpr size_t kOptPosBytes = 10;       // workspace bytes per position
 static_assert(kOptLengths == kWave, "one length per lane");
-static_assert((kOptRing + kOptChunk * kWave) * 4 <= kOptHeads * 2, "ring and staging fit the smaller head table");
+static_assert((kOptRing + kOptChunk * kWave) * 4 <= kHcHeads * 2, "ring and staging fit the smaller head table");
 static_assert(kOptFar < kOptRing && kOptFar - kOptLengths + 1 >= 2 * kOptChunk, "near costs in the ring, far ones final");
-
-template <bool BIG>
-struct OptCfg {
-    typedef uint16_t head_t;             // 16 KiB of LDS: 10 workgroups per CU of 160 KiB
-    static constexpr int kWaves = 2560;
-};
-template <>
-struct OptCfg<true> {
-    typedef uint32_t head_t;             // 32 KiB: 5 per CU
-    static constexpr int kWaves = 1280;
-};
 
 // positions a block of n bytes holds in its slice (cost[n] included)
 __host__ __device__ __forceinline__ int64_t opt_positions(int64_t n) { return (n + 64) & ~(int64_t)63; }
@@ -83,7 +67,7 @@ typedef __attribute__((address_space(3))) uint32_t lds_u32;
 // One block by one wave; all arguments uniform.  Returns the block's size, or
 // 0 if it does not fit in cap.
 template <bool BIG>
-__device__ __forceinline__ int32_t opt_block(__attribute__((address_space(3))) typename OptCfg<BIG>::head_t* head,
+__device__ __forceinline__ int32_t opt_block(__attribute__((address_space(3))) typename HcCfg<BIG ? kHcBig : kHcSmall>::head_t* head,
                                              uint8_t* slice, const uint8_t* src, int32_t n, uint8_t* dst,
                                              int32_t cap, int32_t attempts, uint32_t lane) {
     int32_t op = 0;
@@ -95,24 +79,10 @@ __device__ __forceinline__ int32_t opt_block(__attribute__((address_space(3))) t
     const int32_t mflimit = n - 12, ilimit = n - 11;
 
     // ---- insert
-    for (int32_t i = (int32_t)lane; i < kOptHeads; i += kWave) hc_st(head + i, 0u);
+    for (int32_t i = (int32_t)lane; i < kHcHeads; i += kWave) hc_st(head + i, 0u);
     hc_fence();
-    for (int32_t base = 0; base < ilimit; base += kWave) {
-        const int32_t p = base + (int32_t)lane;
-        const bool act = p < ilimit;
-        uint32_t h = 0;
-        if (act) h = hash4<kOptHashBits>(ld32(src + p));
-        uint64_t below, above;
-        hash_links<kOptHashBits>(act, h, lane, below, above);
-        if (act) {
-            const uint32_t prev = below ? (uint32_t)base + (63u - (uint32_t)__builtin_clzll(below)) + 1u
-                                        : hc_ld(head + h);
-            const uint32_t d = prev ? (uint32_t)p + 1u - prev : 0u;
-            hc_st(chain + p, d > (uint32_t)kOptMaxDist ? 0u : d);
-            if (above == 0) hc_st(head + h, (uint32_t)p + 1u);
-        }
-        hc_fence();
-    }
+    for (int32_t base = 0; base < ilimit; base += kWave)
+        hc_insert_step<false, kNoMask>(head, chain, src, base, ilimit, lane);
 
     // ---- match
     int32_t Lb = 0, Ob = 0;   // L and O of the position before the step's first
@@ -128,7 +98,7 @@ __device__ __forceinline__ int32_t opt_block(__attribute__((address_space(3))) t
             int32_t c = q;
             for (int32_t left = attempts; left > 0 && d != 0; --left) {
                 c -= (int32_t)d;
-                if (c < 0 || q - c > kOptMaxDist) break;
+                if (c < 0 || q - c > kHcMaxDist) break;
                 d = hc_ld(chain + c);   // the next candidate: requested before this one is measured
                 // one load decides most candidates: a match has q's first four bytes, and a longer one
                 // than the best so far (bestL < lim here) also the byte that follows the best
@@ -272,15 +242,15 @@ __global__ __launch_bounds__(64) void opt_parse_kernel(const uint8_t* __restrict
                                                        int32_t* __restrict__ out_len, int64_t nblocks,
                                                        int32_t attempts, uint8_t* __restrict__ work,
                                                        uint64_t slice_bytes) {
-    typedef typename OptCfg<BIG>::head_t head_mem_t;
-    __shared__ __attribute__((aligned(16))) head_mem_t head_mem[kOptHeads];
+    typedef typename HcCfg<BIG ? kHcBig : kHcSmall>::head_t head_mem_t;
+    __shared__ __attribute__((aligned(16))) head_mem_t head_mem[kHcHeads];
     const uint32_t lane = threadIdx.x;
     uint8_t* slice = work + (size_t)blockIdx.x * slice_bytes;
     for (int64_t b = blockIdx.x; b < nblocks; b += gridDim.x) {
         const int32_t n = src_len[b];
-        if ((n > kOptSmallMax) != BIG) continue;   // the other kernel's block (a negative n is refused here)
+        if ((n > kHcSmallMax) != BIG) continue;   // the other kernel's block (a negative n is refused here)
         const int32_t cap = dst_cap[b];
-        if (n < 0 || n > kOptMaxInput || cap < 0 || (uint64_t)opt_positions(n) * kOptPosBytes > slice_bytes) {
+        if (n < 0 || n > kHcMaxInput || cap < 0 || (uint64_t)opt_positions(n) * kOptPosBytes > slice_bytes) {
             if (lane == 0) out_len[b] = 0;
             continue;
         }
@@ -290,20 +260,13 @@ __global__ __launch_bounds__(64) void opt_parse_kernel(const uint8_t* __restrict
     }
 }
 
-// section 9.1's level table; deeper searches for levels 10-12 are not built
-int32_t opt_attempts(int level) {
-    if (level < 1) level = 9;
-    if (level > 9) level = 9;
-    return level < 3 ? 2 : 1 << (level - 1);
-}
-
 }  // namespace
 }  // namespace lz4m
 
 extern "C" size_t lz4m_compress_opt_workspace_size(int64_t n, int32_t max_len) {
     using namespace lz4m;
     if (n <= 0 || max_len < 0) return 0;
-    const int64_t waves = n < OptCfg<false>::kWaves ? n : OptCfg<false>::kWaves;
+    const int64_t waves = n < HcCfg<kHcSmall>::kWaves ? n : HcCfg<kHcSmall>::kWaves;
     return (size_t)waves * (size_t)opt_positions(max_len) * kOptPosBytes;
 }
 
@@ -316,18 +279,18 @@ extern "C" int lz4m_compress_opt_batch(const uint8_t* d_src, const int64_t* d_sr
     if (n == 0) return 0;
     if (d_work == nullptr || ((uintptr_t)d_work & 3u) || work_bytes < lz4m_compress_opt_workspace_size(n, 0))
         return LZ4M_EINVAL;
-    const int32_t attempts = opt_attempts(level);
+    const int32_t attempts = hc_attempts(level);
     hipStream_t st = (hipStream_t)stream;
     // one slice per wave of the wider grid, a multiple of 64 positions; both
     // kernels walk the whole batch and take their own blocks
-    const uint32_t small_grid = (uint32_t)(n < OptCfg<false>::kWaves ? n : OptCfg<false>::kWaves);
+    const uint32_t small_grid = (uint32_t)(n < HcCfg<kHcSmall>::kWaves ? n : HcCfg<kHcSmall>::kWaves);
     const uint64_t unit = 64 * kOptPosBytes;
     const uint64_t slice_bytes = (uint64_t)work_bytes / small_grid / unit * unit;
     hipLaunchKernelGGL(opt_parse_kernel<false>, dim3(small_grid), dim3(64), 0, st, d_src, d_src_off, d_src_len, d_dst,
                        d_dst_off, d_dst_cap, d_out_len, n, attempts, (uint8_t*)d_work, slice_bytes);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
-    const uint32_t big_grid = (uint32_t)(n < OptCfg<true>::kWaves ? n : OptCfg<true>::kWaves);
+    const uint32_t big_grid = (uint32_t)(n < HcCfg<kHcBig>::kWaves ? n : HcCfg<kHcBig>::kWaves);
     hipLaunchKernelGGL(opt_parse_kernel<true>, dim3(big_grid), dim3(64), 0, st, d_src, d_src_off, d_src_len, d_dst,
                        d_dst_off, d_dst_cap, d_out_len, n, attempts, (uint8_t*)d_work, slice_bytes);
     return (int)hipGetLastError();

@@ -2,7 +2,9 @@
  * tests/hc_model/opt_model.c -- CPU model of the price-based optimal LZ4 block
  * parse of lz4m_compress_opt_batch (python-lz4_amd/csrc/lz4m_opt.hip), as
  * DESIGN.md section 9.7 defines it.  The HIP kernels must produce these bytes.
- * Plain C99, no dependency; the tests build it with gcc at run time.
+ * Plain C99; it builds on the tables, the level table and the sequence writer
+ * of hc_model.c, which it includes (so this file alone is the translation
+ * unit, and the HC models and the decoder come with it).
  *
  * The parse, serially (n >= 13; shorter blocks are one literal run):
  *   tables    h(p) = (LE32(src + p) * 2654435761) >> (32 - 13); head[h] the
@@ -29,50 +31,23 @@
  *             result is 0 and dst is not touched.
  */
 #include <assert.h>
-#include <stdint.h>
-#include <stdlib.h>
-#include <string.h>
 
-#define OPT_HASH_BITS 13
-#define OPT_MAX_DIST 65535
+#include "hc_model.c"   /* the tables, the level table, the sequence writer, the decoder */
+
 #define OPT_LENGTHS 64   /* K: match lengths priced per position */
 
-int opt_model_attempts(int level) {
-    if (level < 1) level = 9;
-    if (level > 9) level = 9;          /* deeper searches for levels 10-12 are not modelled */
-    return level < 3 ? 2 : 1 << (level - 1);
-}
-
-static uint32_t le32(const uint8_t* p) {
-    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-}
-
-static uint32_t opt_hash(const uint8_t* p) { return (le32(p) * 2654435761u) >> (32 - OPT_HASH_BITS); }
-
-static int32_t ext_bytes(int32_t v) { return v >= 15 ? 1 + (v - 15) / 255 : 0; }
-
-static uint8_t* put_ext(uint8_t* op, int32_t v) {
-    if (v >= 15) {
-        v -= 15;
-        for (; v >= 255; v -= 255) *op++ = 255;
-        *op++ = (uint8_t)v;
-    }
-    return op;
-}
-
 /* L[q], O[q] for every q < n (0: no match) */
-static void opt_matches(const uint8_t* src, int32_t n, int attempts, uint32_t* head, uint16_t* chain, uint16_t* L,
-                        uint16_t* O) {
-    const int32_t mflimit = n - 12;
+static void opt_matches(hc_state* s, uint16_t* L, uint16_t* O) {
+    const uint8_t* src = s->src;
+    const int32_t n = s->n, mflimit = n - 12;
     int32_t pl = 0, po = 0;   /* L and O of q - 1 */
     memset(L, 0, (size_t)n * sizeof(uint16_t));
     memset(O, 0, (size_t)n * sizeof(uint16_t));
     for (int32_t q = 0; q <= mflimit; ++q) {
         const int32_t lim = n - 5 - q < 65535 ? n - 5 - q : 65535;
-        const uint32_t h = opt_hash(src + q);
         int32_t best = 0, off = 0;
-        uint32_t cur = head[h];
-        for (int left = attempts; left > 0 && cur != 0 && q - (int32_t)(cur - 1) <= OPT_MAX_DIST; --left) {
+        uint32_t cur = s->head[hc_hash(src + q)];
+        for (int left = s->attempts; left > 0 && cur != 0 && q - (int32_t)(cur - 1) <= HC_MAX_DIST; --left) {
             const int32_t c = (int32_t)(cur - 1);
             /* the match of q - 1 at the same distance, less its first byte, is known to hold here */
             int32_t fwd = q - c == po && pl > 1 ? pl - 1 : 0;
@@ -87,20 +62,14 @@ static void opt_matches(const uint8_t* src, int32_t n, int attempts, uint32_t* h
                 off = q - c;
                 if (best == lim) break;   /* nothing longer exists */
             }
-            const uint32_t d = chain[c];
+            const uint32_t d = s->chain[c & 0xFFFF];
             cur = d ? cur - d : 0;
         }
         L[q] = (uint16_t)best;
         O[q] = (uint16_t)off;
         pl = best;
         po = off;
-        /* insert q */
-        {
-            const uint32_t prev = head[h];
-            const uint32_t d = prev ? (uint32_t)q + 1u - prev : 0u;
-            chain[q] = (uint16_t)(d > OPT_MAX_DIST ? 0u : d);
-            head[h] = (uint32_t)q + 1u;
-        }
+        hc_insert_to(s, q + 1);
     }
 }
 
@@ -136,60 +105,44 @@ static int32_t opt_prices(int32_t n, const uint16_t* L, uint16_t* M, int32_t* co
     return cost[0];
 }
 
-static uint8_t* opt_put_seq(uint8_t* o, const uint8_t* lits, int32_t ll, int32_t off, int32_t ml) {
-    const int32_t mt = ml ? (ml - 4 < 15 ? ml - 4 : 15) : 0;
-    *o++ = (uint8_t)(((ll < 15 ? ll : 15) << 4) | mt);
-    o = put_ext(o, ll);
-    if (ll) memcpy(o, lits, (size_t)ll);
-    o += ll;
-    if (ml) {
-        *o++ = (uint8_t)(off & 0xFF);
-        *o++ = (uint8_t)(off >> 8);
-        o = put_ext(o, ml - 4);
-    }
-    return o;
-}
-
-/* the block's size (its cost[0]) without writing it; 0 on a bad argument */
+/* the block's size (its cost[0]), written to dst if `write`; 0 on a bad
+ * argument or, writing, where it does not fit in cap */
 static int opt_run(const uint8_t* src, int n, uint8_t* dst, int cap, int level, int write) {
-    if (n < 0 || cap < 0 || n > 0x7E000000) return 0;
-    if (n < 13) {
-        const int size = 1 + n;   /* a token and n < 15 literals */
-        if (!write) return size;
-        if (size > cap) return 0;
-        opt_put_seq(dst, src, n, 0, 0);
-        return size;
+    if (n < 0 || cap < 0 || n > HC_MAX_INPUT) return 0;
+    int64_t op = 0;
+    if (n < 13) {   /* a token and n < 15 literals */
+        if (!write) return 1 + n;
+        return hc_emit(src, n, 0, 0, dst, &op, cap) ? (int)op : 0;
     }
-    uint32_t* head = (uint32_t*)calloc((size_t)1 << OPT_HASH_BITS, sizeof(uint32_t));
-    uint16_t* chain = (uint16_t*)calloc((size_t)n, sizeof(uint16_t));
+    hc_state s;
+    const int tables = hc_open(&s, src, n, level);
     uint16_t* L = (uint16_t*)malloc((size_t)n * sizeof(uint16_t));
     uint16_t* O = (uint16_t*)malloc((size_t)n * sizeof(uint16_t));
     uint16_t* M = (uint16_t*)malloc((size_t)n * sizeof(uint16_t));
     int32_t* cost = (int32_t*)malloc(((size_t)n + 1) * sizeof(int32_t));
     int size = 0;
-    if (head && chain && L && O && M && cost) {
-        opt_matches(src, n, opt_model_attempts(level), head, chain, L, O);
+    if (tables && L && O && M && cost) {
+        opt_matches(&s, L, O);
         size = opt_prices(n, L, M, cost);
         if (write && size > cap) size = 0;
         if (write && size) {
-            uint8_t* o = dst;
             int32_t anchor = 0, p = 0;
-            while (p < n) {
+            int fits = 1;
+            while (p < n && fits) {
                 if (M[p]) {
-                    o = opt_put_seq(o, src + anchor, p - anchor, O[p], M[p]);
+                    fits = hc_emit(src + anchor, p - anchor, O[p], M[p], dst, &op, size);
                     p += M[p];
                     anchor = p;
                 } else {
                     ++p;
                 }
             }
-            o = opt_put_seq(o, src + anchor, n - anchor, 0, 0);
-            assert(o - dst == size);
-            if (o - dst != size) abort();
+            fits = fits && hc_emit(src + anchor, n - anchor, 0, 0, dst, &op, size);
+            assert(fits && op == size);
+            if (!fits || op != size) abort();
         }
     }
-    free(head);
-    free(chain);
+    hc_close(&s);
     free(L);
     free(O);
     free(M);
@@ -203,44 +156,3 @@ int opt_model_compress(const uint8_t* src, int n, uint8_t* dst, int cap, int lev
 
 /* cost[0] of the price pass alone (what opt_model_compress's size must equal) */
 int opt_model_cost(const uint8_t* src, int n, int level) { return opt_run(src, n, NULL, 0, level, 0); }
-
-/* A small safe decoder (the check program decodes the model's output with it):
- * returns the decoded size, or -1 on any malformed or overlong input. */
-int opt_model_decode(const uint8_t* src, int n, uint8_t* dst, int cap) {
-    int64_t ip = 0, op = 0;
-    if (n <= 0) return -1;
-    for (;;) {
-        if (ip >= n) return -1;
-        const uint32_t tok = src[ip++];
-        int64_t ll = tok >> 4;
-        if (ll == 15) {
-            uint32_t b;
-            do {
-                if (ip >= n) return -1;
-                b = src[ip++];
-                ll += b;
-            } while (b == 255);
-        }
-        if (ll > n - ip || ll > cap - op) return -1;
-        if (ll) memcpy(dst + op, src + ip, (size_t)ll);
-        ip += ll;
-        op += ll;
-        if (ip == n) return (tok & 15) ? -1 : (int)op;
-        if (n - ip < 2) return -1;
-        const int64_t off = (int64_t)src[ip] | ((int64_t)src[ip + 1] << 8);
-        ip += 2;
-        int64_t ml = tok & 15;
-        if (ml == 15) {
-            uint32_t b;
-            do {
-                if (ip >= n) return -1;
-                b = src[ip++];
-                ml += b;
-            } while (b == 255);
-        }
-        ml += 4;
-        if (off == 0 || off > op || ml > cap - op) return -1;
-        for (int64_t k = 0; k < ml; ++k) dst[op + k] = dst[op + k - off];
-        op += ml;
-    }
-}

@@ -1,35 +1,18 @@
 """Shared pieces of tests/test_hc_prefix_model.py and tests/test_gpu_hc_prefix.py:
 the CPU model of the HC parse of a block with a prefix
-(tests/hc_model/hc_model_prefix.c, built with gcc into hc_support's temporary
-directory on first use) and the (prefix, block) cases both files use."""
-import ctypes as C
+(hc_model_compress_prefix of tests/hc_model/hc_model.c, hc_support's library)
+and the (prefix, block) cases both files use."""
 import functools
-import os
-import subprocess
 
 import numpy as np
 
 import hc_support as H
-
-PREFIX_C = os.path.join(H.MODEL_DIR, "hc_model_prefix.c")
-PREFIX_CHECK_C = os.path.join(H.MODEL_DIR, "hc_model_prefix_check.c")
 
 PREFIX_LENGTHS = (1, 3, 4, 7, 8, 63, 64, 65, 4096, 65535, 65536)
 BLOCK_LENGTHS = (0, 1, 12, 13, 14, 64, 65, 4096, 65536, 65537)
 PREFIX_MAX = 65536
 FRAME_BLOCK = 65536          # block_size_id 4
 FRAME_OVERHEAD = 15 + 4      # header with the content size, end mark (no checksums); plus 4 per block
-
-
-@functools.lru_cache(maxsize=None)
-def model_lib():
-    so = os.path.join(H.build_dir(), "libhc_model_prefix.so")
-    subprocess.run(["gcc", "-O2", "-std=c99", "-Wall", "-Werror", "-fPIC", "-shared", PREFIX_C, "-o", so],
-                   check=True, capture_output=True, text=True)
-    lib = C.CDLL(so)
-    lib.hc_model_compress_prefix.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int]
-    lib.hc_model_compress_prefix.restype = C.c_int
-    return lib
 
 
 def model_compress_at(buf: np.ndarray, start: int, n: int, prefix_len: int, level: int,
@@ -39,8 +22,8 @@ def model_compress_at(buf: np.ndarray, start: int, n: int, prefix_len: int, leve
     assert 0 <= prefix_len <= min(start, PREFIX_MAX) and start + n <= buf.size
     cap = H.compress_bound(n) if cap is None else cap
     dst = np.zeros(max(cap, 1), dtype=np.uint8)
-    r = model_lib().hc_model_compress_prefix(buf.ctypes.data + start - prefix_len, prefix_len, n, dst.ctypes.data,
-                                             cap, level)
+    r = H.model_lib().hc_model_compress_prefix(buf.ctypes.data + start - prefix_len, prefix_len, n, dst.ctypes.data,
+                                               cap, level)
     return None if r <= 0 else dst[:r].tobytes()
 
 

@@ -3,24 +3,17 @@ model of the optimal parse (tests/hc_model/opt_model.c, built with gcc into
 hc_support's temporary directory on first use).  The inputs are hc_support's."""
 import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 
 import hc_support as H
 
-MODEL_C = os.path.join(H.MODEL_DIR, "opt_model.c")
-CHECK_C = os.path.join(H.MODEL_DIR, "opt_model_check.c")
 ALL_KINDS = H.KINDS + ("runs", "random")
 
 
 @functools.lru_cache(maxsize=None)
 def model_lib():
-    so = os.path.join(H.build_dir(), "libopt_model.so")
-    subprocess.run(["gcc", "-O2", "-std=c99", "-Wall", "-Werror", "-fPIC", "-shared", MODEL_C, "-o", so],
-                   check=True, capture_output=True, text=True)
-    lib = C.CDLL(so)
+    lib = H._build(H.OPT_MODEL_C, "libopt_model.so")
     lib.opt_model_compress.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]
     lib.opt_model_compress.restype = C.c_int
     lib.opt_model_cost.argtypes = [C.c_void_p, C.c_int, C.c_int]
@@ -28,13 +21,9 @@ def model_lib():
     return lib
 
 
-def _array(data) -> np.ndarray:
-    return np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data)
-
-
 @functools.lru_cache(maxsize=None)
 def _compress_full(data: bytes, level: int) -> bytes:
-    src = _array(data)
+    src = H._array(data)
     cap = H.compress_bound(src.size)
     dst = np.zeros(cap, dtype=np.uint8)
     r = model_lib().opt_model_compress(src.ctypes.data if src.size else None, src.size, dst.ctypes.data, cap, level)
@@ -47,7 +36,7 @@ def model_compress(data, level: int, cap: int | None = None) -> bytes | None:
     Blocks at the full bound are computed once per (data, level) and shared."""
     if cap is None:
         return _compress_full(bytes(data), level)
-    src = _array(data)
+    src = H._array(data)
     dst = np.full(cap + 1, 0xA5, dtype=np.uint8)
     r = model_lib().opt_model_compress(src.ctypes.data if src.size else None, src.size, dst.ctypes.data, cap, level)
     assert dst[cap] == 0xA5   # nothing past the capacity
@@ -56,5 +45,5 @@ def model_compress(data, level: int, cap: int | None = None) -> bytes | None:
 
 def model_cost(data, level: int) -> int:
     """cost[0] of the model's price pass."""
-    src = _array(data)
+    src = H._array(data)
     return model_lib().opt_model_cost(src.ctypes.data if src.size else None, src.size, level)

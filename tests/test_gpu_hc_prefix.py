@@ -1,15 +1,14 @@
 """GPU tests of the HC compressor with a prefix (hc_prefix_kernel,
 lz4m_compress_hc_dict_batch, compress_batch(dict_len=),
 compress_many(mode="high_compression", dict=), lz4.frame.compress_device(
-parse="hc")): its bytes equal the CPU model (tests/hc_model/hc_model_prefix.c)
+parse="hc")): its bytes equal the CPU model (hc_model_compress_prefix of
+tests/hc_model/hc_model.c)
 and decode on the device with the prefix as dictionary; an absent prefix gives
 the old entry point's bytes; batches are independent of their layout; limited
 output; C-ABI argument checks; dictionaries through compress_many; HC frames,
 linked and independent; the kernels' resource report."""
 import json
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -17,13 +16,14 @@ import torch
 
 import hc_prefix_support as HP
 import hc_support as H
-from conftest import GOLDEN, ROOT
+from conftest import GOLDEN
 
 import lz4.block
 import lz4.frame
 from lz4 import _native as N, _synth
 
 HC = "high_compression"
+_outputs = H.outputs
 
 
 class Batch:
@@ -68,11 +68,6 @@ class Batch:
         t = lambda v, dt: torch.tensor(v, dtype=dt, device=dev)   # noqa: E731
         return (torch.from_numpy(self.host().copy()).to(dev), t(self.off, torch.int64), t(self.len, torch.int32),
                 t(self.dl, torch.int32))
-
-
-def _outputs(dst, dst_off, out_len):
-    d, o, n = dst.cpu().numpy(), dst_off.cpu().numpy(), out_len.cpu().numpy()
-    return [d[int(a):int(a) + int(k)].tobytes() for a, k in zip(o, n)]
 
 
 def _assert_decodes(batch: Batch, src, off, ln, dst, dst_off, out_len):
@@ -382,17 +377,11 @@ def test_frame_arguments_and_unchanged_paths(gpu):
 
 
 def test_hc_prefix_kernels_use_no_scratch():
-    """The compiler's resource report of lz4m_hc.hip (kept by the csrc Makefile): the two
+    """The compiler's resource report of lz4m_hc.hip (kept by the csrc Makefile): the
     three hc_prefix_kernel instances use 0 bytes of scratch."""
-    csrc = os.path.join(ROOT, "python-lz4_amd", "csrc")
-    subprocess.run(["make", "-s", "-C", csrc], check=True, capture_output=True)
-    seen, name = 0, None
-    for line in open(os.path.join(csrc, "build", "lz4m_hc.res")):
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-        m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
-        if m and name and "hc_prefix_kernel" in name:
-            assert int(m.group(1)) == 0, f"{name} uses {m.group(1)} B/lane of scratch"
+    seen = 0
+    for name, scratch in H.scratch_report("lz4m_hc.res"):
+        if "hc_prefix_kernel" in name:
+            assert scratch == 0, f"{name} uses {scratch} B/lane of scratch"
             seen += 1
     assert seen == 3   # prefix + block up to 64 KiB, up to 128 KiB, and beyond

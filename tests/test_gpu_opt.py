@@ -4,9 +4,6 @@ the CPU model of the parse (tests/hc_model/opt_model.c) and decode on the
 device; batches are independent of their layout and of the workspace's
 contents; limited output; slot containment under a scattered layout; C-ABI
 argument checks; the block and frame APIs; the kernels' resource report."""
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,44 +12,18 @@ import torch
 import hc_support as H
 import layout_support as LS
 import opt_support as P
-from conftest import ROOT
-
 import lz4.block
 import lz4.frame
-from lz4 import _native as N, _synth
+from lz4 import _native as N
 
 OPT = "optimal"
-
-
-def _pack(blocks, dev, first: int = 0, gap: int = 0):
-    """Blocks back to back (``gap`` bytes between them, the first at offset ``first``)."""
-    lens = np.array([len(b) for b in blocks], dtype=np.int32)
-    offs = np.full(len(blocks), first, dtype=np.int64)
-    offs[1:] += np.cumsum(lens[:-1].astype(np.int64) + gap)
-    buf = np.zeros(int(offs[-1] + lens[-1]) + 16, dtype=np.uint8)
-    for b, o in zip(blocks, offs):
-        buf[o:o + len(b)] = np.frombuffer(b, dtype=np.uint8)
-    return torch.from_numpy(buf).to(dev), torch.from_numpy(offs).to(dev), torch.from_numpy(lens).to(dev)
-
-
-def _outputs(dst, dst_off, out_len):
-    d, o, n = dst.cpu().numpy(), dst_off.cpu().numpy(), out_len.cpu().numpy()
-    return [d[int(a):int(a) + int(k)].tobytes() for a, k in zip(o, n)]
+_pack, _outputs, _assert_decodes = H.pack, H.outputs, H.assert_decodes
 
 
 def _compress(blocks, dev, level, **kw):
     src, off, ln = _pack(blocks, dev)
     dst, dst_off, out_len = lz4.block.compress_batch(src, off, ln, mode=OPT, compression=level, **kw)
     return src, off, ln, dst, dst_off, out_len
-
-
-def _assert_decodes(src, ln, dst, dst_off, out_len):
-    """Every block decodes on the device to its input (blocks packed back to back in src)."""
-    assert bool((out_len > 0).all())
-    back, _, status = lz4.block.decompress_batch(dst, dst_off, out_len, ln)
-    assert torch.equal(status, ln)
-    total = int(ln.sum().item())
-    assert torch.equal(back[:total], src[:total])
 
 
 def _launch(lib, src, off, ln, dst, dst_off, cap, out_len, level, work):
@@ -80,12 +51,7 @@ def test_kernel_bytes_equal_the_model(gpu, equality_inputs, level):
 
 @pytest.fixture(scope="module")
 def mixed_batch():
-    """4096 blocks of 0..70000 bytes cut from the silesia mix (seeded)."""
-    pool = _synth.blocks(256, "silesia", seed=77, block=70000)
-    rng = np.random.default_rng(4096)
-    lens = rng.integers(0, 70001, size=4096)
-    lens[:4] = (0, 70000, 13, 12)
-    return [pool[i % 256, :int(n)].tobytes() for i, n in enumerate(lens)]
+    return H.mixed_batch()
 
 
 @pytest.mark.gpu
@@ -293,18 +259,9 @@ def test_frame_api(gpu):
 
 def test_opt_kernels_use_no_scratch():
     """The compiler's resource report of lz4m_opt.hip (kept by the csrc Makefile): 0 bytes of scratch."""
-    csrc = os.path.join(ROOT, "python-lz4_amd", "csrc")
-    subprocess.run(["make", "-s", "-C", csrc], check=True, capture_output=True)
-    rep = os.path.join(csrc, "build", "lz4m_opt.res")
-    assert os.path.exists(rep)
-    seen, name = 0, None
-    for line in open(rep):
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            assert "hc_compress_kernel" not in name
-        m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
-        if m and name:
-            assert int(m.group(1)) == 0, f"{name} uses {m.group(1)} B/lane of scratch"
-            seen += 1
+    seen = 0
+    for name, scratch in H.scratch_report("lz4m_opt.res"):
+        assert "hc_compress_kernel" not in name
+        assert scratch == 0, f"{name} uses {scratch} B/lane of scratch"
+        seen += 1
     assert seen == 2   # the <= 64 KiB kernel and the long-block kernel

@@ -6,7 +6,6 @@ sanitizer run of the stand-alone check program."""
 import ctypes as C
 import json
 import os
-import subprocess
 
 import pytest
 
@@ -123,13 +122,9 @@ def test_golden_sizes_match_reference_build():
 
 
 def test_model_check_program_under_sanitizers():
-    """hc_model_check (its own main, ASan + UBSan) runs the model over the
+    """model_check (its own main, ASan + UBSan; one run shared by the three
+    model test files) runs the HC model over the
     edge cases with exactly sized buffers and exits 0."""
-    exe = os.path.join(H.build_dir(), "hc_model_check")
-    r = subprocess.run(["gcc", "-O1", "-g", "-std=c99", "-Wall", "-fno-omit-frame-pointer",
-                        "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", H.CHECK_C, H.MODEL_C,
-                        "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    r = subprocess.run([exe], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
+    r = H.check_program()
     assert r.returncode == 0, r.stdout + r.stderr
     assert "hc_model_check: ok" in r.stdout

@@ -1,5 +1,5 @@
 """CPU tests of the model of the HC parse with a prefix
-(tests/hc_model/hc_model_prefix.c): the serial definition of DESIGN.md section
+(hc_model_compress_prefix of tests/hc_model/hc_model.c): the serial definition of DESIGN.md section
 9.5 that lz4m_compress_hc_dict_batch reproduces byte for byte
 (tests/test_gpu_hc_prefix.py).  An empty prefix gives the old model's bytes;
 validity against the oracle's decoder with the prefix as dictionary; the edge
@@ -7,7 +7,6 @@ cases of the prefix; limited output; a sanitizer run of the stand-alone check
 program; sizes of linked frames against the reference's LZ4F_compressFrame."""
 import json
 import os
-import subprocess
 
 import pytest
 
@@ -112,16 +111,13 @@ def test_model_limited_output():
 
 
 def test_model_check_program_under_sanitizers():
-    """hc_model_prefix_check (its own main, ASan + UBSan) runs the model over
+    """model_check (its own main, ASan + UBSan; one run shared by the three
+    model test files) runs the prefix model over
     prefixes and blocks in exactly sized buffers and exits 0."""
-    exe = os.path.join(H.build_dir(), "hc_model_prefix_check")
-    r = subprocess.run(["gcc", "-O1", "-g", "-std=c99", "-Wall", "-fno-omit-frame-pointer",
-                        "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", HP.PREFIX_CHECK_C,
-                        HP.PREFIX_C, "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    r = subprocess.run([exe], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
+    r = H.check_program()
     assert r.returncode == 0, r.stdout + r.stderr
     assert "hc_model_prefix_check: ok" in r.stdout
+
 
 
 @pytest.fixture(scope="module")

@@ -7,7 +7,6 @@ sanitizer run of the stand-alone check program."""
 import ctypes as C
 import json
 import os
-import subprocess
 
 import pytest
 
@@ -130,13 +129,9 @@ def test_golden_sizes_match_reference_build():
 
 
 def test_model_check_program_under_sanitizers():
-    """opt_model_check (its own main, ASan + UBSan) runs the model over the
-    edge cases with exactly sized buffers and exits 0."""
-    exe = os.path.join(H.build_dir(), "opt_model_check")
-    r = subprocess.run(["gcc", "-O2", "-g", "-std=c99", "-Wall", "-fno-omit-frame-pointer",
-                        "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", P.CHECK_C, P.MODEL_C,
-                        "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    r = subprocess.run([exe], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
+    """model_check (its own main, ASan + UBSan; one run shared by the three
+    model test files) runs the optimal model over
+    the edge cases with exactly sized buffers and exits 0."""
+    r = H.check_program()
     assert r.returncode == 0, r.stdout + r.stderr
     assert "opt_model_check: ok" in r.stdout
