@@ -1373,6 +1373,10 @@ extern "C" int lz4m_compress_worker_launch(Mailbox* mb, uint8_t* hd, uint8_t* db
     return (int)hipGetLastError();
 }
 
+// the acceleration LZ4_compress_fast accepts (lz4.c:1350-1351); one wavefront per block on a grid the kernels stride
+static inline int clamp_accel(int a) { return a < 1 ? 1 : a > 65537 ? 65537 : a; }
+static inline uint32_t wave_grid(int64_t n) { return (uint32_t)(n < (1ll << 30) ? n : (1ll << 30)); }
+
 extern "C" int lz4m_compress_bound(int input_size) {
     if ((unsigned)input_size > (unsigned)kMaxInput) return 0;
     return input_size + input_size / 255 + 16;
@@ -1383,8 +1387,7 @@ extern "C" int lz4m_compress_solo(const uint8_t* d_src, int32_t len, uint8_t* d_
                                   int32_t* h_done, lz4m_stream_t stream) {
     if (len < 0 || len > kSoloMax || cap < 0) return LZ4M_EINVAL;
     if (const int e = lds_order_check()) return e;
-    if (acceleration < 1) acceleration = 1;        // lz4.c:1350-1351
-    if (acceleration > 65537) acceleration = 65537;
+    acceleration = clamp_accel(acceleration);
     hipStream_t s = (hipStream_t)stream;
     auto go = [&](auto v_tag) {
         constexpr int V = decltype(v_tag)::value;
@@ -1416,9 +1419,8 @@ extern "C" int lz4m_compress_batch(const uint8_t* d_src, const int64_t* d_src_of
     if (n < 0) return LZ4M_EINVAL;
     if (n == 0) return 0;
     if (const int e = lds_order_check()) return e;
-    if (acceleration < 1) acceleration = 1;        // lz4.c:1350-1351
-    if (acceleration > 65537) acceleration = 65537;
-    const uint32_t grid = (uint32_t)(n < (1ll << 30) ? n : (1ll << 30));
+    acceleration = clamp_accel(acceleration);
+    const uint32_t grid = wave_grid(n);
     hipStream_t s = (hipStream_t)stream;
     // acceleration 1 (the python-lz4 default) runs the 32-bit-schedule instance
     auto exact = [&](auto v_tag, int only) {
@@ -1490,9 +1492,8 @@ static int compress_dict_launch(const uint8_t* d_src, const int64_t* d_src_off, 
     if (n < 0) return LZ4M_EINVAL;
     if (n == 0) return 0;
     if (const int e = lds_order_check()) return e;
-    if (acceleration < 1) acceleration = 1;
-    if (acceleration > 65537) acceleration = 65537;
-    const uint32_t grid = (uint32_t)(n < (1ll << 30) ? n : (1ll << 30));
+    acceleration = clamp_accel(acceleration);
+    const uint32_t grid = wave_grid(n);
     hipLaunchKernelGGL(compress_dict_kernel, dim3(grid), dim3(64), 0, (hipStream_t)stream, d_src, d_src_off,
                        d_src_len, d_dict_len, d_dst, d_dst_off, d_dst_cap, d_out_len, n, acceleration, prefix);
     return (int)hipGetLastError();
@@ -1541,16 +1542,14 @@ extern "C" int lz4m_compress_linked_batch(const uint8_t* d_src, const int64_t* d
     if (mode == LZ4M_LINKED_SPECULATIVE && (d_work == nullptr || work_bytes < lz4m_compress_linked_workspace_size(n)))
         return LZ4M_EINVAL;
     if (const int e = lds_order_check()) return e;
-    if (acceleration < 1) acceleration = 1;
-    if (acceleration > 65537) acceleration = 65537;
+    acceleration = clamp_accel(acceleration);
     hipStream_t s = (hipStream_t)stream;
-    const uint32_t grid = (uint32_t)(n < (1ll << 30) ? n : (1ll << 30));
+    const uint32_t grid = wave_grid(n);
     if (mode == LZ4M_LINKED_SERIAL) {
         hipLaunchKernelGGL(compress_chain_kernel, dim3(grid), dim3(64), 0, s, d_src, d_src_off, d_src_len, d_link,
                            d_dst, d_dst_off, d_dst_cap, d_out_len, n, acceleration);
         return (int)hipGetLastError();
     }
-    if (d_work == nullptr || work_bytes < lz4m_compress_linked_workspace_size(n)) return LZ4M_EINVAL;
     uint8_t* base = (uint8_t*)d_work;
     int32_t* counters = (int32_t*)base;
     uint32_t* tb[2] = {(uint32_t*)(base + 64), (uint32_t*)(base + 64 + (size_t)n * 16384)};

@@ -1256,6 +1256,20 @@ int decoder_env() {
 
 }  // namespace
 
+// The one-wavefront-per-block (hist) decoder's launch: four blocks per workgroup on a grid the kernel strides over.
+// DICT: block i's dictionary ends at dst + ddelta + dst_off[i]; SOLO: a single call's one block, also to solo_out.
+template <bool DICT, bool SOLO = false>
+static int launch_hist(const uint8_t* d_src, const int64_t* d_src_off, const int32_t* d_src_len, uint8_t* d_dst,
+                       const int64_t* d_dst_off, const int32_t* d_dst_cap, int32_t* d_status, int64_t n,
+                       hipStream_t st, const int32_t* d_dict_len = nullptr, int64_t ddelta = 0,
+                       uint8_t* solo_out = nullptr, int32_t* solo_done = nullptr) {
+    const int64_t grid = (n + 3) / 4;
+    hipLaunchKernelGGL((hist_decompress_kernel<DICT, SOLO>), dim3((uint32_t)(grid < 65536 ? grid : 65536)), dim3(256),
+                       0, st, d_src, d_src_off, d_src_len, d_dst, d_dst_off, d_dst_cap, d_status, n, d_dict_len, ddelta,
+                       solo_out, solo_done);
+    return (int)hipGetLastError();
+}
+
 extern "C" size_t lz4m_decompress_workspace_bytes(void) { return 64; }
 
 extern "C" size_t lz4m_decompress_workspace_size(int64_t n, int64_t src_bytes) {
@@ -1293,10 +1307,7 @@ extern "C" int lz4m_decompress_batch_sel(const uint8_t* d_src, const int64_t* d_
                            d_src_len, d_dst, d_dst_off, d_dst_cap, nullptr, nullptr, nullptr, d_status, n, meta);
         return (int)hipGetLastError();
     }
-    const int64_t grid = (n + 3) / 4;
-    hipLaunchKernelGGL(hist_decompress_kernel<false>, dim3((uint32_t)(grid < 65536 ? grid : 65536)), dim3(256), 0, st,
-                       d_src, d_src_off, d_src_len, d_dst, d_dst_off, d_dst_cap, d_status, n, nullptr, (int64_t)0, nullptr, nullptr);
-    return (int)hipGetLastError();
+    return launch_hist<false>(d_src, d_src_off, d_src_len, d_dst, d_dst_off, d_dst_cap, d_status, n, st);
 }
 
 extern "C" int lz4m_decompress_solo(const uint8_t* d_src, const int64_t* d_src_off, const int32_t* d_src_len,
@@ -1304,9 +1315,8 @@ extern "C" int lz4m_decompress_solo(const uint8_t* d_src, const int64_t* d_src_o
                                     int32_t* d_status, int32_t src_len_host, uint8_t* h_out, int32_t* h_done,
                                     lz4m_stream_t stream) {
     if (src_len_host < 0 || src_len_host > kSoloIn - 64) return LZ4M_EINVAL;
-    hipLaunchKernelGGL((hist_decompress_kernel<false, true>), dim3(1), dim3(256), 0, (hipStream_t)stream, d_src,
-                       d_src_off, d_src_len, d_dst, d_dst_off, d_dst_cap, d_status, (int64_t)1, nullptr, (int64_t)0, h_out, h_done);
-    return (int)hipGetLastError();
+    return launch_hist<false, true>(d_src, d_src_off, d_src_len, d_dst, d_dst_off, d_dst_cap, d_status, 1,
+                                    (hipStream_t)stream, nullptr, 0, h_out, h_done);
 }
 
 extern "C" int lz4m_worker_launch(int kind, Mailbox* mb, uint8_t* hd, uint8_t* dbuf, uint64_t idle_ticks,
@@ -1331,11 +1341,8 @@ extern "C" int lz4m_decompress_batch(const uint8_t* d_src, const int64_t* d_src_
     if (n < 0) return LZ4M_EINVAL;
     if (n == 0) return 0;
     // no scratch: the one-wavefront-per-block decoder (any batch size)
-    const int64_t grid = (n + 3) / 4;
-    hipLaunchKernelGGL(hist_decompress_kernel<false>, dim3((uint32_t)(grid < 65536 ? grid : 65536)), dim3(256), 0,
-                       (hipStream_t)stream, d_src, d_src_off, d_src_len, d_dst, d_dst_off, d_dst_cap, d_status, n,
-                       nullptr, (int64_t)0, nullptr, nullptr);
-    return (int)hipGetLastError();
+    return launch_hist<false>(d_src, d_src_off, d_src_len, d_dst, d_dst_off, d_dst_cap, d_status, n,
+                              (hipStream_t)stream);
 }
 
 extern "C" int lz4m_decompress_batch_dict(const uint8_t* d_src, const int64_t* d_src_off, const int32_t* d_src_len,
@@ -1358,12 +1365,8 @@ extern "C" int lz4m_decompress_batch_prefix(const uint8_t* d_src, const int64_t*
                                             int32_t* d_status, int64_t n, lz4m_stream_t stream) {
     if (n < 0 || (n > 0 && d_dict_base == nullptr)) return LZ4M_EINVAL;
     if (n == 0) return 0;
-    const int64_t grid = (n + 3) / 4;
-    const int64_t delta = (int64_t)((intptr_t)d_dict_base - (intptr_t)d_dst);
-    hipLaunchKernelGGL(hist_decompress_kernel<true>, dim3((uint32_t)(grid < 65536 ? grid : 65536)), dim3(256), 0,
-                       (hipStream_t)stream, d_src, d_src_off, d_src_len, d_dst, d_dst_off, d_dst_cap, d_status, n,
-                       d_dict_len, delta, nullptr, nullptr);
-    return (int)hipGetLastError();
+    return launch_hist<true>(d_src, d_src_off, d_src_len, d_dst, d_dst_off, d_dst_cap, d_status, n,
+                             (hipStream_t)stream, d_dict_len, (int64_t)((intptr_t)d_dict_base - (intptr_t)d_dst));
 }
 
 extern "C" int lz4m_decompress_chain(const uint8_t* d_src, const int64_t* d_src_off, const int32_t* d_src_len,

@@ -6,6 +6,7 @@
 // header and endmark -- runs on one lane per frame, the frames side by side;
 // everything per block (compression, decoding, record emission, checksums)
 // runs in the block-batched launchers over the blocks of all frames at once.
+//   one frame: frame_scan (lz4.frame.decompress_device), the same walk
 //   decode:   frames_scan (count the records) -> exclusive scan of the counts
 //             -> frames_records (fill the global per-block arrays)
 //   compress: frames_plan (block-size id, block count, linked) -> scan ->
@@ -98,9 +99,20 @@ __device__ FrameHead parse_head(const uint8_t* p, int64_t n) {
     return h;
 }
 
-// The record walk of frame_scan_kernel (lz4frame.c:1643-1701, 1926-1965) from
-// `pos` of a frame of n bytes at p.  EMIT: store record k's fields at base + k.
-template <bool EMIT>
+// not a frame status: walk_records<true> stopped at `limit` records, before an endmark
+constexpr int32_t kWalkAtLimit = -1;
+
+// LZ4F_decompress's walk over the block records (lz4frame.c:1643-1701 block
+// headers, 1926-1965 endmark and content checksum) from `pos` of a frame of n
+// bytes at p: the one walk of the tree, for one frame (frame_scan_kernel) and
+// for a batch (frames_scan_kernel counts, frames_records_kernel stores).
+// Serial by construction -- each record's position depends on the previous
+// one's size -- so one lane walks a frame: one dependent HBM read per record
+// (measured 0.25 us per record, stores included: 4 ms for the 16 384 records
+// of a 1 GiB frame of 64 KiB blocks, profiles/frame_refactor.json).
+// EMIT: store record k's fields at base + k (rec_crc too if CRC), at most
+// `limit` records.
+template <bool EMIT, bool CRC = EMIT>
 __device__ __forceinline__ int32_t walk_records(const uint8_t* p, int64_t n, int64_t pos, int crc,
                                                 int content_checksum, int64_t max_block, int32_t& status,
                                                 int64_t& end, int64_t& cpos, int64_t abs, int64_t base,
@@ -140,16 +152,48 @@ __device__ __forceinline__ int32_t walk_records(const uint8_t* p, int64_t n, int
             break;
         }
         if (EMIT) {
-            if (k == limit) break;   // never past the count the first pass took
+            if (k == limit) {   // never past the caller's arrays (the count the first pass took)
+                status = kWalkAtLimit;
+                break;
+            }
             rec_pos[base + k] = abs + pos;
             rec_len[base + k] = (int32_t)size;
             rec_raw[base + k] = (uint8_t)(hdr >> 31);
-            rec_crc[base + k] = crc ? abs + pos + size : -1;
+            if (CRC) rec_crc[base + k] = crc ? abs + pos + size : -1;
         }
         ++k;
         pos += size + crc;
     }
     return (int32_t)k;
+}
+
+// lz4m_frame_scan: one frame, one lane.  result = {records, state, end,
+// content-checksum position}, the state as include/lz4m.h documents it.
+// The records' checksum positions (rec_crc, may be null) follow from their
+// positions and sizes and are filled by the whole workgroup after the walk: the
+// walk waits for its stores with each dependent read, and a fourth store in its
+// loop measured +28 ns on 245 ns per record.
+__global__ __launch_bounds__(256) void frame_scan_kernel(const uint8_t* __restrict__ frame, int64_t n, int64_t pos,
+                                                         int crc, int content_checksum, int32_t max_block,
+                                                         int64_t max_rec, int64_t* __restrict__ rec_pos,
+                                                         int32_t* __restrict__ rec_len, uint8_t* __restrict__ rec_raw,
+                                                         int64_t* __restrict__ rec_crc,
+                                                         int64_t* __restrict__ result) {
+    __shared__ int32_t records;
+    if (threadIdx.x == 0) {
+        int32_t st;
+        int64_t end, cpos;
+        records = walk_records<true, false>(frame, n, pos, crc, content_checksum, max_block, st, end, cpos, 0, 0,
+                                            rec_pos, rec_len, rec_raw, nullptr, max_rec);
+        result[0] = records;
+        result[1] = st == LZ4M_FRAME_OK ? 0 : st == LZ4M_FRAME_TRUNCATED ? 1 : st == LZ4M_FRAME_BLOCK_TOO_LARGE ? 2
+                  : st == LZ4M_FRAME_CONTENT_CHECKSUM_MISSING ? 3 : 4;   // 4: kWalkAtLimit, more than max_rec records
+        result[2] = end;
+        result[3] = cpos;
+    }
+    if (rec_crc == nullptr) return;
+    __syncthreads();   // (orders lane 0's stores before the workgroup's reads of them)
+    for (int32_t k = threadIdx.x; k < records; k += blockDim.x) rec_crc[k] = crc ? rec_pos[k] + rec_len[k] : -1;
 }
 
 __global__ __launch_bounds__(64) void frames_scan_kernel(const uint8_t* __restrict__ buf,
@@ -330,6 +374,17 @@ using namespace lz4m;
 
 namespace {
 inline dim3 lanes(int64_t n, int per) { return dim3((uint32_t)((n + per - 1) / per)); }
+}
+
+extern "C" int lz4m_frame_scan(const uint8_t* d_frame, int64_t frame_len, int64_t pos, int block_checksum,
+                               int content_checksum, int32_t max_block, int64_t max_rec, int64_t* d_rec_pos,
+                               int32_t* d_rec_len, uint8_t* d_rec_raw, int64_t* d_rec_crc, int64_t* d_result,
+                               lz4m_stream_t stream) {
+    if (frame_len < 0 || pos < 0 || max_block < 0 || max_rec < 0 || !d_result) return LZ4M_EINVAL;
+    hipLaunchKernelGGL(frame_scan_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, d_frame, frame_len, pos,
+                       block_checksum ? 4 : 0, content_checksum, max_block, max_rec, d_rec_pos, d_rec_len, d_rec_raw,
+                       d_rec_crc, d_result);
+    return (int)hipGetLastError();
 }
 
 extern "C" int lz4m_frames_scan(const uint8_t* d_buf, const int64_t* d_frame_off, const int64_t* d_frame_len,

@@ -75,7 +75,7 @@ def _declare(lib) -> None:
         "lz4m_gather": ([vp, vp, vp, vp, vp, i64, vp], i32),
         "lz4m_frame_block_sizes": ([vp, vp, i32, vp, i64, vp], i32),
         "lz4m_frame_emit": ([vp, vp, vp, vp, vp, vp, vp, vp, i32, i64, vp], i32),
-        "lz4m_frame_scan": ([vp, i64, i64, i32, i32, i32, i64, vp, vp, vp, vp, vp], i32),
+        "lz4m_frame_scan": ([vp, i64, i64, i32, i32, i32, i64, vp, vp, vp, vp, vp, vp], i32),
         "lz4m_frames_scan": ([vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp], i32),
         "lz4m_frames_records": ([vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp], i32),
         "lz4m_decompress_chains": ([vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp], i32),
@@ -342,6 +342,47 @@ def launch_compress_linked(src, src_off, src_len, link, dst, dst_off, dst_cap, o
     check(rc, "lz4m_compress_linked_batch")
 
 
+class Parse(collections.namedtuple("Parse", "launcher table accel level history prefix",
+                                    defaults=(TABLE_AUTO, 1, 0, "", False))):
+    """What lz4.block's and lz4.frame's ``resolve_parse`` make of a compression
+    call's arguments; ``launch_blocks`` dispatches on it.  launcher: "table"
+    (the exact and parallel parses, by ``table`` and ``accel``), "hc" or "opt"
+    (at ``level``).  history: which array goes with the blocks -- "" none;
+    "hist" the length of each block's dictionary or history, whose last 64 KiB
+    precede the block in the source (``prefix``: taken in prefix mode); "link"
+    the link flags of linked frames' blocks; "shared" one PreparedDict."""
+    __slots__ = ()
+
+
+def _launch_hc(p, a, x, max_len, spec, s):
+    launch_compress_hc(*a, p.level, s, max_len=max_len or 0, dict_len=x)
+
+
+# (launcher, history) -> launch(parse, the eight batch arguments, extra, max_len, speculative, stream); a pair that
+# is not here is a parse no resolver gives
+_BLOCK_LAUNCH = {
+    ("table", ""): lambda p, a, x, max_len, spec, s: launch_compress(*a, p.table, p.accel, s, max_len=max_len),
+    ("table", "hist"): lambda p, a, x, max_len, spec, s: launch_compress_dict(*a[:3], x, *a[3:], p.accel, s,
+                                                                              prefix=p.prefix),
+    ("table", "link"): lambda p, a, x, max_len, spec, s: launch_compress_linked(
+        *a[:3], x, *a[3:], p.accel, LINKED_SPECULATIVE if spec else LINKED_SERIAL, s),
+    ("table", "shared"): lambda p, a, x, max_len, spec, s: launch_pcompress_dict(*a[:3], x.tail, x.table, *a[3:], s),
+    ("hc", ""): _launch_hc, ("hc", "hist"): _launch_hc,
+    ("opt", ""): lambda p, a, x, max_len, spec, s: launch_compress_opt(*a, p.level, s, max_len=max_len),
+}
+
+
+def launch_blocks(parse: Parse, src, src_off, src_len, dst, dst_off, dst_cap, out_len, n, *, extra=None,
+                  max_len: int | None = None, speculative: bool = False, stream=None) -> None:
+    """The one launch of block compression: n blocks with the parse ``parse``.
+    ``extra`` is what ``parse.history`` names; ``max_len`` the longest block
+    (sizes the workspaces of the large-block parallel, HC and optimal parses;
+    None: unknown); ``speculative``: linked blocks compress speculatively in
+    parallel, not one wavefront per frame."""
+    _BLOCK_LAUNCH[parse.launcher, parse.history](parse, (src, src_off, src_len, dst, dst_off, dst_cap, out_len, n),
+                                                 extra, max_len, speculative, stream)
+
+
 def launch_xxh32_batch(src, off, length, seed, out, n, stream=None) -> None:
     rc = lib().lz4m_xxh32_batch(ptr(src), ptr(off), ptr(length), seed & 0xFFFFFFFF, ptr(out), n, stream_ptr(stream))
     check(rc, "lz4m_xxh32_batch")
@@ -381,10 +422,10 @@ def frame_emit(raw, raw_off, raw_len, cmp, cmp_off, cmp_len, frame, frame_off, b
 
 
 def frame_scan(frame, frame_len, pos, block_checksum, content_checksum, max_block, max_rec, rec_pos, rec_len,
-               rec_raw, result, stream=None) -> None:
+               rec_raw, rec_crc, result, stream=None) -> None:
     rc = lib().lz4m_frame_scan(ptr(frame), frame_len, pos, int(bool(block_checksum)), int(bool(content_checksum)),
-                               max_block, max_rec, ptr(rec_pos), ptr(rec_len), ptr(rec_raw), ptr(result),
-                               stream_ptr(stream))
+                               max_block, max_rec, ptr(rec_pos), ptr(rec_len), ptr(rec_raw), ptr(rec_crc),
+                               ptr(result), stream_ptr(stream))
     check(rc, "lz4m_frame_scan")
 
 

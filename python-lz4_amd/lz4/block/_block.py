@@ -6,7 +6,9 @@ messages (``_block.c:127-400``).  Every call runs the HIP kernels of
 ``_lz4m.so``; single calls pay one H2D + launch + D2H, so the batched
 entry points (``compress_batch`` / ``decompress_batch`` on device tensors,
 ``compress_many`` / ``decompress_many`` on host buffers) are the throughput
-path.
+path.  The three compression calls share ``resolve_parse`` (arguments -> one
+parse description, or the argument error) and ``_native.launch_blocks`` (the
+launch that description names), as the frame calls do.
 """
 from __future__ import annotations
 
@@ -59,40 +61,6 @@ def _buffer(obj, name: str = "source") -> memoryview:
     if not mv.c_contiguous:
         raise BufferError("memoryview: underlying buffer is not C-contiguous")
     return mv.cast("B") if mv.format != "B" or mv.ndim != 1 else mv
-
-
-def _mode_accel(mode, acceleration: int) -> int | None:
-    """The acceleration of the non-HC modes; None for 'high_compression' and 'optimal'."""
-    if not isinstance(mode, str):
-        raise TypeError(f"compress() argument 'mode' must be str, not {type(mode).__name__}")
-    if mode == "default":
-        return 1
-    if mode == "fast":
-        return acceleration
-    if mode in ("high_compression", "optimal"):
-        return None
-    raise ValueError(f"Invalid mode argument: {mode}. Must be one of: standard, fast, high_compression, optimal")
-
-
-def _hc_mode(mode) -> bool:
-    """``mode`` of the batched calls: "default" (the exact compressors, chosen
-    by their own ``table`` / ``accel`` arguments), "high_compression" or
-    "optimal" (true for both; _opt_mode tells them apart)."""
-    if mode == "default":
-        return False
-    if mode in ("high_compression", "optimal"):
-        return True
-    raise ValueError(f"Invalid mode argument: {mode}. Must be one of: default, high_compression, optimal")
-
-
-def _opt_mode(mode, dict=None, dict_len=None) -> bool:
-    """True for mode="optimal", which takes no dictionary."""
-    if mode != "optimal":
-        return False
-    if dict is not None or dict_len is not None:
-        raise NotImplementedError("mode='optimal' with a dictionary (dict= / dict_len=) is not built: the optimal "
-                                  "parse has no history; use mode='high_compression' with a dictionary")
-    return True
 
 
 def _cap_and_skip(view: memoryview, uncompressed_size: int):
@@ -173,36 +141,28 @@ def compress(source, mode="default", store_size=True, acceleration=1, compressio
         d = _buffer(dict, "dict")
         if d.nbytes > INT_MAX:
             raise OverflowError("Dictionary too large for LZ4 API")
-    accel = _mode_accel(mode, acceleration)
-    if accel is None:
-        _opt_mode(mode, dict=d)
-        if d is not None:
-            raise NotImplementedError(
-                "mode='high_compression' with dict= (LZ4_loadDictHC) is not built on the MI355X codec; "
-                "compress without a dictionary, or use mode='default' or mode='fast' with dict=")
-        out = compress_many([src], store_size=bool(store_size), as_bytearray=bool(return_bytearray),
-                            mode=mode, compression=compression)[0]
-        if out is None:
-            raise LZ4BlockError("Compression failed")
-        return out
-    if d is None:   # one call: lz4m_compress_block_api (one launch on mapped pinned staging)
+    p = resolve_parse(mode, accel=acceleration, compression=compression, dict=d, single=True)
+    if p.launcher == "table" and d is None:   # one call: lz4m_compress_block_api (one launch on mapped pinned staging)
         N.require_device()
         n = src.nbytes
         hdr = _HDR if store_size else 0
-        p = C.c_void_p()
+        ptr = C.c_void_p()
         # the output (after the size header) stays in the thread's pinned buffer: one copy into the result
-        r = N.lib().lz4m_compress_block_api_staged(N.host_addr(src), n, max(N.compress_bound(n), 1), accel, hdr,
-                                                   C.byref(p))
+        r = N.lib().lz4m_compress_block_api_staged(N.host_addr(src), n, max(N.compress_bound(n), 1), p.accel, hdr,
+                                                   C.byref(ptr))
         if r <= 0:
             raise LZ4BlockError("Compression failed")
-        out = C.string_at(p.value, hdr + r)
+        out = C.string_at(ptr.value, hdr + r)
         return bytearray(out) if return_bytearray else out
-    # dictionary memory that ends where the source begins: the reference's
-    # LZ4_compress_fast_continue sees dictEnd == source and takes prefix mode
-    # (lz4.c:1671-1676; LZ4_loadDict keeps no dictionary below 8 bytes)
-    prefix = d.nbytes >= 8 and src.nbytes > 0 and N.host_addr(d) + d.nbytes == N.host_addr(src)
-    out = compress_many([src], accel=accel, store_size=bool(store_size), as_bytearray=bool(return_bytearray),
-                        dict=d, dict_prefix=prefix)[0]
+    if p.launcher != "table":
+        how = {"mode": mode, "compression": compression}
+    else:
+        # dictionary memory that ends where the source begins: the reference's
+        # LZ4_compress_fast_continue sees dictEnd == source and takes prefix mode
+        # (lz4.c:1671-1676; LZ4_loadDict keeps no dictionary below 8 bytes)
+        prefix = d.nbytes >= 8 and src.nbytes > 0 and N.host_addr(d) + d.nbytes == N.host_addr(src)
+        how = {"accel": p.accel, "dict": d, "dict_prefix": prefix}
+    out = compress_many([src], store_size=bool(store_size), as_bytearray=bool(return_bytearray), **how)[0]
     if out is None:
         raise LZ4BlockError("Compression failed")
     return out
@@ -412,6 +372,56 @@ def prepare_dict(dict, stream=None) -> PreparedDict:
     return _prepare_dict(dict, stream)
 
 
+_TABLES = {"block": N.TABLE_U32_HASH5, "default": N.TABLE_AUTO, "u16": N.TABLE_U16_HASH4}
+_MODES = {False: ("default", "high_compression", "optimal"), True: ("default", "fast", "high_compression", "optimal")}
+
+
+def resolve_parse(mode="default", *, accel=1, compression=9, table=N.TABLE_U32_HASH5, dict=None,
+                  dict_prefix=False, dict_len=None, dict_buf=None, single=False) -> N.Parse:
+    """The parse the arguments of ``compress`` (``single``: the reference's
+    mode names, no HC dictionary), ``compress_many`` or ``compress_batch`` ask
+    for, as the description ``N.launch_blocks`` takes, or the call's exception
+    for arguments that do not go together.  Pure: no data, no launch."""
+    if single and not isinstance(mode, str):
+        raise TypeError(f"compress() argument 'mode' must be str, not {type(mode).__name__}")
+    if mode not in _MODES[single]:
+        names = "standard, fast, high_compression, optimal" if single else "default, high_compression, optimal"
+        raise ValueError(f"Invalid mode argument: {mode}. Must be one of: {names}")
+    if mode == "optimal":
+        if dict is not None or dict_len is not None or dict_buf is not None:
+            raise NotImplementedError("mode='optimal' with a dictionary (dict= / dict_len=) is not built: the optimal "
+                                      "parse has no history; use mode='high_compression' with a dictionary")
+        return N.Parse("opt", level=_c_int(compression, "compression"))
+    if mode == "high_compression" and single and dict is not None:
+        raise NotImplementedError(
+            "mode='high_compression' with dict= (LZ4_loadDictHC) is not built on the MI355X codec; "
+            "compress without a dictionary, or use mode='default' or mode='fast' with dict=")
+    level = _c_int(compression, "compression")
+    hc = mode == "high_compression"
+    shared = dict is not None and not hc and not dict_prefix and table == N.PARSE_PARALLEL
+    if isinstance(dict, PreparedDict) and not shared:
+        raise ValueError("a PreparedDict is only valid with table=PARSE_PARALLEL, mode='default' and no dict_prefix")
+    if dict_buf is not None:
+        if hc:
+            raise ValueError("dict_buf is not valid with mode='high_compression' (use dict_len)")
+        if dict_len is not None:
+            raise ValueError("dict_buf (one shared dictionary) and dict_len (one per block) exclude each other")
+        if table != N.PARSE_PARALLEL:
+            raise ValueError("dict_buf is only valid with table=PARSE_PARALLEL")
+        shared = True
+    if dict_len is not None and not hc:
+        raise ValueError("dict_len is only valid with mode='high_compression'")
+    history = "shared" if shared else "hist" if dict is not None or dict_len is not None else ""
+    if hc:
+        return N.Parse("hc", level=level, history=history)
+    accel = 1 if single and mode == "default" else int(accel)
+    if history == "shared":
+        return N.Parse("table", N.PARSE_PARALLEL, history=history)
+    if history == "hist":   # the dictionary compressor has one table, lz4.block.compress's
+        return N.Parse("table", N.TABLE_U32_HASH5, accel, history=history, prefix=bool(dict_prefix))
+    return N.Parse("table", int(_TABLES.get(table, table)), accel)
+
+
 def compress_many(blocks, accel: int = 1, store_size: bool = True, as_bytearray: bool = False,
                   table: int = N.TABLE_U32_HASH5, dict=None, dict_prefix: bool = False,
                   mode: str = "default", compression: int = 9):
@@ -439,12 +449,8 @@ def compress_many(blocks, accel: int = 1, store_size: bool = True, as_bytearray:
     The dictionary is uploaded and hashed once per call -- not staged with
     every block -- or not at all when ``dict`` is a ``PreparedDict``
     (``prepare_dict``), which only this combination accepts."""
-    hc = _hc_mode(mode)
-    opt = _opt_mode(mode, dict=dict)
-    compression = _c_int(compression, "compression")
-    shared = dict is not None and not hc and not dict_prefix and table == N.PARSE_PARALLEL
-    if isinstance(dict, PreparedDict) and not shared:
-        raise ValueError("a PreparedDict is only valid with table=PARSE_PARALLEL, mode='default' and no dict_prefix")
+    p = resolve_parse(mode, accel=accel, compression=compression, table=table, dict=dict, dict_prefix=dict_prefix)
+    staged = p.history == "hist"   # the dictionary's last 64 KiB are staged in front of each block
     views = [_buffer(b) for b in blocks]
     dev = N.device()
     n = len(views)
@@ -453,33 +459,25 @@ def compress_many(blocks, accel: int = 1, store_size: bool = True, as_bytearray:
     lens = [v.nbytes for v in views]
     caps = [max(N.compress_bound(L), 1) for L in lens]
     d_off = _excl_offsets(caps)
-    if dict is None or shared:
+    extra = None
+    if not staged:
         offs = _excl_offsets(lens)
         payload = views
+        if p.history == "shared":
+            extra = _prepare_dict(dict)
     else:
         dv = _buffer(dict, "dict")
         # LZ4_loadDict keeps the last 64 KiB (lz4.c:1568) and nothing of a dictionary below 8 bytes; HC keeps any
-        tail = dv[-65536:] if dv.nbytes >= 8 or hc else dv[:0]
+        small = dv.nbytes < 8 and p.launcher != "hc"
+        tail = dv[:0] if small else dv[-65536:]
         t = tail.nbytes
         offs = np.arange(1, n + 1, dtype=np.int64) * t + _excl_offsets(lens)
         payload = [x for v in views for x in (tail, v)]
+        extra = torch.full((n,), dv.nbytes, dtype=torch.int32, device=dev)
+        p = p._replace(prefix=p.prefix and not small)
     lay, h, d = _stage_in(dev, payload, offs, lens, d_off, caps)
-    d_src, src_off, src_len, d_dst, dst_off, dst_cap, out_len = _dev_views(lay, d, n)
-    dict_len = None if dict is None or shared else torch.full((n,), dv.nbytes, dtype=torch.int32, device=dev)
-    if shared:
-        pd = _prepare_dict(dict)
-        N.launch_pcompress_dict(d_src, src_off, src_len, pd.tail, pd.table, d_dst, dst_off, dst_cap, out_len, n)
-    elif opt:
-        N.launch_compress_opt(d_src, src_off, src_len, d_dst, dst_off, dst_cap, out_len, n, compression,
-                              max_len=max(lens))
-    elif hc:
-        N.launch_compress_hc(d_src, src_off, src_len, d_dst, dst_off, dst_cap, out_len, n, compression,
-                             max_len=max(lens), dict_len=dict_len)
-    elif dict is None:
-        N.launch_compress(d_src, src_off, src_len, d_dst, dst_off, dst_cap, out_len, n, table, accel)
-    else:
-        N.launch_compress_dict(d_src, src_off, src_len, dict_len, d_dst, dst_off, dst_cap, out_len, n, accel,
-                               prefix=dict_prefix and dv.nbytes >= 8)
+    # (with max_len the parallel parse's large-block launch is the segmented one: the frame calls' choice only)
+    N.launch_blocks(p, *_dev_views(lay, d, n), n, extra=extra, max_len=None if p.launcher == "table" else max(lens))
     olen, host = _stage_out(lay, h, d, n)
     if n >= _MANY and sum(L for L in olen if L > 0) >= _MANY_BYTES:
         return _results_many(host, d_off, [L if L > 0 else -1 for L in olen], lens if store_size else None,
@@ -601,19 +599,8 @@ def compress_batch(src: torch.Tensor, src_off: torch.Tensor, src_len: torch.Tens
     the blocks (up to 64 KiB each) decode with it as their dictionary.  Below
     4 bytes it changes nothing.
     """
-    hc = _hc_mode(mode)
-    opt = _opt_mode(mode, dict=dict_buf, dict_len=dict_len)
-    compression = _c_int(compression, "compression")
-    if dict_buf is not None:
-        if hc:
-            raise ValueError("dict_buf is not valid with mode='high_compression' (use dict_len)")
-        if dict_len is not None:
-            raise ValueError("dict_buf (one shared dictionary) and dict_len (one per block) exclude each other")
-        if table != N.PARSE_PARALLEL:
-            raise ValueError("dict_buf is only valid with table=PARSE_PARALLEL")
-    if dict_len is not None and not hc:
-        raise ValueError("dict_len is only valid with mode='high_compression'")
-    tab = {"block": N.TABLE_U32_HASH5, "default": N.TABLE_AUTO, "u16": N.TABLE_U16_HASH4}.get(table, table)
+    p = resolve_parse(mode, accel=acceleration, compression=compression, table=table, dict_len=dict_len,
+                      dict_buf=dict_buf)
     n = src_off.numel()
     dev = src.device
     if dst_cap is None:
@@ -624,21 +611,13 @@ def compress_batch(src: torch.Tensor, src_off: torch.Tensor, src_len: torch.Tens
         total = int((dst_off[-1] + dst_cap[-1]).item()) if n else 1
         dst = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
     out_len = torch.empty(n, dtype=torch.int32, device=dev)
-    if opt:
-        if n:
-            N.launch_compress_opt(src, src_off, src_len, dst, dst_off, dst_cap, out_len, n, compression, stream)
-    elif hc:
-        if n:
-            N.launch_compress_hc(src, src_off, src_len, dst, dst_off, dst_cap, out_len, n, compression, stream,
-                                 dict_len=None if dict_len is None else dict_len.to(torch.int32))
-    elif dict_buf is not None:
-        if n:
-            pd = _prepare_dict(dict_buf, stream, copy=False)
-            N.launch_pcompress_dict(src, src_off, src_len, pd.tail, pd.table, dst, dst_off, dst_cap, out_len, n,
-                                    stream)
-    else:
-        N.launch_compress(src, src_off, src_len, dst, dst_off, dst_cap, out_len, n, int(tab), int(acceleration),
-                          stream)
+    if n:
+        extra = None
+        if p.history == "shared":
+            extra = _prepare_dict(dict_buf, stream, copy=False)
+        elif p.history == "hist":
+            extra = dict_len.to(torch.int32)
+        N.launch_blocks(p, src, src_off, src_len, dst, dst_off, dst_cap, out_len, n, extra=extra, stream=stream)
     return dst, dst_off, out_len
 
 

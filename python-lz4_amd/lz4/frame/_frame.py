@@ -30,6 +30,13 @@ LE32 block records); every byte-level operation runs on the GPU:
   launches, linked frames one wavefront each, content checksums on the
   device.
 
+The single-frame and the batched calls share the compression pipeline (a block
+plan -- built on the host for one frame --, the block stage ``_compress_blocks``
+with the parse ``resolve_parse`` made of the arguments, record sizes, a scan,
+record emission: a batched frame has the single call's bytes by construction)
+and the record walk (one device loop).  Separate on purpose (DESIGN.md section
+10): the content hash and the decode strategy, as the two items above say.
+
 Scope notes: every frame ``compress`` writes is byte-identical
 to the reference's (``parse="parallel"`` on ``compress_device`` trades that
 for speed); HC levels (>= 3) and the chunked / context streaming API are
@@ -96,9 +103,12 @@ class _HashThread(threading.Thread):
 
 
 # ------------------------------------------------------------------ header
-# linked frames with at least this many blocks compress speculatively in
-# parallel (lz4m_compress_linked_batch); shorter ones one wavefront per frame
+# Linked frames with at least _SPEC_MIN_BLOCKS blocks on average, in a call of
+# fewer than _BATCH_SPEC_MAX_FRAMES linked frames, compress speculatively (a
+# wavefront per block, lz4m_compress_linked_batch); otherwise one wavefront per
+# frame, which is parallel over the frames
 _SPEC_MIN_BLOCKS = 4
+_BATCH_SPEC_MAX_FRAMES = 256
 
 
 def _optimal_bsid(requested: int, size: int) -> int:
@@ -236,8 +246,18 @@ def _host_wait(stream) -> None:
     ev.synchronize()
 
 
-def _parse_level(parse, compression_level):
-    """(level, acceleration) of a device compression call, or its argument error."""
+class LinkedOptimalError(NotImplementedError, ValueError):
+    """parse="optimal" asked for linked blocks: a combination that is not
+    built (NotImplementedError) and, until it is, a bad value of ``parse`` for
+    a linked frame (ValueError, what an unknown parse raises)."""
+
+
+def resolve_parse(parse="exact", compression_level=0, block_linked=True) -> N.Parse:
+    """The parse a device compression call's arguments ask for, as the
+    description ``N.launch_blocks`` takes, or the call's argument error.  Its
+    history names the block plan's array that goes with a linked frame's blocks
+    ("link": one stream per frame, lz4frame.c:865-871; "hist": HC history; the
+    parallel parse has none).  Pure: no data, no launch."""
     level = int(compression_level)
     if parse not in ("exact", "parallel", "hc", "optimal"):
         raise ValueError("parse must be 'exact', 'parallel', 'hc' or 'optimal'")
@@ -246,19 +266,32 @@ def _parse_level(parse, compression_level):
             raise ValueError(f"parse='{parse}' needs compression_level >= 3 (levels 0-2 are the fast compressor)")
     elif level >= 3:
         raise NotImplementedError("LZ4 HC compression levels (>= 3) are outside the MI355X codec's scope")
-    return level, (-level + 1 if level < 0 else 1)             # lz4frame.c:855
+    if parse == "optimal":
+        if block_linked:
+            raise LinkedOptimalError("parse='optimal' has no history: block_linked=True is not built "
+                                     "(pass block_linked=False, or parse='hc' for linked blocks)")
+        return N.Parse("opt", level=level)
+    if parse == "hc":
+        return N.Parse("hc", level=level, history="hist" if block_linked else "")
+    accel = -level + 1 if level < 0 else 1                     # lz4frame.c:855
+    if parse == "parallel":
+        return N.Parse("table", N.PARSE_PARALLEL, accel, level)
+    return N.Parse("table", N.TABLE_AUTO, accel, level, history="link" if block_linked else "")
 
 
-class LinkedOptimalError(NotImplementedError, ValueError):
-    """parse="optimal" asked for linked blocks: a combination that is not
-    built (NotImplementedError) and, until it is, a bad value of ``parse`` for
-    a linked frame (ValueError, what an unknown parse raises)."""
-
-
-def _no_linked_optimal(parse, block_linked) -> None:
-    if parse == "optimal" and block_linked:
-        raise LinkedOptimalError("parse='optimal' has no history: block_linked=True is not built "
-                                 "(pass block_linked=False, or parse='hc' for linked blocks)")
+def _plan_one(n, bsize, nb, history, dev) -> dict:
+    """frames_plan_blocks' arrays for one frame of n bytes in nb blocks, built on the host (no plan kernel, no
+    read-back); of link and hist, the one a linked frame's parse asks for (``history``)."""
+    raw_off = torch.arange(nb, dtype=torch.int64, device=dev) * bsize
+    raw_len = torch.full((nb,), bsize, dtype=torch.int32, device=dev)
+    raw_len[-1] = n - (nb - 1) * bsize
+    P = {"raw_off": raw_off, "raw_len": raw_len, "cap": raw_len - 1}   # lz4frame.c:835: dstCapacity = srcSize - 1
+    if history == "link":                                      # one stream across the blocks
+        P["link"] = torch.ones(nb, dtype=torch.int32, device=dev)
+        P["link"][0] = 0
+    elif history == "hist":                                    # the input before the block, at most 64 KiB
+        P["hist"] = raw_off.clamp(max=65536).to(torch.int32)
+    return P
 
 
 def _compress_frame(d_src, n=None, *, compression_level=0, block_size=0, content_checksum=False,
@@ -267,10 +300,11 @@ def _compress_frame(d_src, n=None, *, compression_level=0, block_size=0, content
     """compress_device, also returning the block records:
     (frame, {"data_off", "stored_len", "raw"}) with device tensors giving, per
     block, the payload position in the frame, its stored length and whether
-    it is stored raw (None when the input is empty)."""
+    it is stored raw (None when the input is empty).  The pipeline of
+    compress_batch for one frame: the plan and the header come from the host,
+    the content hash runs on a host thread."""
     n = d_src.numel() if n is None else int(n)
-    level, accel = _parse_level(parse, compression_level)
-    _no_linked_optimal(parse, block_linked)
+    p = resolve_parse(parse, compression_level, block_linked)
     bsid = _optimal_bsid(int(block_size), n)
     if bsid == 0:
         bsid = BLOCKSIZE_MAX64KB                               # LZ4F_BLOCKSIZEID_DEFAULT
@@ -297,35 +331,15 @@ def _compress_frame(d_src, n=None, *, compression_level=0, block_size=0, content
             hthread = _HashThread(lambda: N.xxh32_of_device(d_src, n, wait_event=ready))
             hthread.start()
     if nb:
-        raw_off = torch.arange(nb, dtype=torch.int64, device=dev) * bsize
-        raw_len = torch.full((nb,), bsize, dtype=torch.int32, device=dev)
-        raw_len[-1] = n - (nb - 1) * bsize
-        cap = raw_len - 1                                      # lz4frame.c:835: dstCapacity = srcSize - 1
+        P = _plan_one(n, bsize, nb, p.history if linked else "", dev)
+        raw_off, raw_len = P["raw_off"], P["raw_len"]
         slot = N.compress_bound(bsize)
         cmp = torch.empty(nb * slot, dtype=torch.uint8, device=dev)
         cmp_off = torch.arange(nb, dtype=torch.int64, device=dev) * slot
         cmp_len = torch.empty(nb, dtype=torch.int32, device=dev)
-        if parse == "hc":
-            # linked: block i's history is the input before it, at most 64 KiB: every block in one launch
-            hist = raw_off.clamp(max=65536).to(torch.int32) if linked else None
-            N.launch_compress_hc(d_src, raw_off, raw_len, cmp, cmp_off, cap, cmp_len, nb, level, stream,
-                                 max_len=bsize, dict_len=hist)
-        elif parse == "optimal":
-            N.launch_compress_opt(d_src, raw_off, raw_len, cmp, cmp_off, cap, cmp_len, nb, level, stream,
-                                  max_len=min(bsize, n))
-        elif parse == "exact" and linked:   # one stream across the blocks (lz4frame.c:865-871)
-            link = torch.ones(nb, dtype=torch.int32, device=dev)
-            link[0] = 0
-            mode = N.LINKED_SPECULATIVE if nb >= _SPEC_MIN_BLOCKS else N.LINKED_SERIAL
-            N.launch_compress_linked(d_src, raw_off, raw_len, link, cmp, cmp_off, cap, cmp_len, nb, accel,
-                                     mode=mode, stream=stream)
-        else:
-            if parse == "exact":
-                table = N.TABLE_AUTO
-            else:
-                table = N.PARSE_PARALLEL if bsize <= 65536 else N.PARSE_PARALLEL_LARGE
-            N.launch_compress(d_src, raw_off, raw_len, cmp, cmp_off, cap, cmp_len, nb, table, accel, stream,
-                              max_len=bsize)
+        # max_len sizes workspaces: the block size, for the optimal parse the longest block
+        _compress_blocks(d_src, P, cmp, cmp_off, cmp_len, p, linked, bsize > 65536,
+                         min(bsize, n) if p.launcher == "opt" else bsize, 1, stream)
         rec_len = torch.empty(nb, dtype=torch.int32, device=dev)
         N.frame_block_sizes(raw_len, cmp_len, block_checksum, rec_len, nb, stream)
         frame_off = N.exclusive_scan(rec_len, stream=stream)
@@ -631,23 +645,23 @@ def decompress_device(d_frame: torch.Tensor, n: int | None = None, stream=None) 
         info, hsize = None, 0
     if info is None or info["skippable"] or n <= hsize:
         return _via_host_path(d_frame, n)   # errors and skippable frames
-    crc = 4 if info["block_checksum"] else 0
     max_rec = n // 64 + 1024
     rec_pos = torch.empty(max_rec, dtype=torch.int64, device=dev)
     rec_len = torch.empty(max_rec, dtype=torch.int32, device=dev)
     rec_raw = torch.empty(max_rec, dtype=torch.uint8, device=dev)
+    # (the records' checksum positions come from the scan too; nothing reads them without block checksums)
+    rec_crc = torch.empty(max_rec, dtype=torch.int64, device=dev) if info["block_checksum"] else None
     res = torch.zeros(4, dtype=torch.int64, device=dev)
     N.frame_scan(d_frame, n, hsize, info["block_checksum"], info["content_checksum"], info["block_size"], max_rec,
-                 rec_pos, rec_len, rec_raw, res, stream)
+                 rec_pos, rec_len, rec_raw, rec_crc, res, stream)
     nb, st, _end, cpos = (int(v) for v in res.cpu().tolist())
     if st != 0:   # malformed / truncated (or > max_rec records)
         return _via_host_path(d_frame, n)
     out_t, total, first_err, got = None, 0, None, None
     if nb:
-        crc_pos = rec_pos[:nb] + rec_len[:nb].to(torch.int64) if crc else torch.full((nb,), -1, dtype=torch.int64,
-                                                                                      device=dev)
         out_t, total, first_err, got = _decode_records(d_frame, info, nb, rec_pos[:nb], rec_len[:nb],
-                                                       rec_raw[:nb].to(torch.bool), crc_pos,
+                                                       rec_raw[:nb].to(torch.bool),
+                                                       None if rec_crc is None else rec_crc[:nb],
                                                        follow_hash=bool(info["content_checksum"]))
     _frame_errors(first_err, ("end", _end, cpos if cpos >= 0 else None), info, total)
     if info["content_checksum"]:
@@ -731,7 +745,8 @@ def _first_error(bad_dec, crc_bad):
 def _decode_records(d_frame, info, nb, c_off, c_len, raw_mask, crc_pos, follow_hash=False):
     """Decode nb block records of a frame in device memory: payload at
     c_off[i] (int64), stored size c_len[i] (int32), raw_mask[i] = stored
-    uncompressed, crc_pos[i] = position of its LE32 block checksum or -1.
+    uncompressed, crc_pos[i] = position of its LE32 block checksum (unused,
+    and may be None, without block checksums).
     Returns (out tensor, total decoded bytes, first error or None, the
     content XXH32 of the output or None when the caller must hash it).
 
@@ -900,10 +915,6 @@ def _linked_status(d_frame, c_off, c_len, raw_mask, out, status, nb, maxb, st):
 # the blocks of all frames share the block-batched launches.  The number of
 # launches and host synchronisations of a call does not depend on the number
 # of frames: the host reads back totals (block count, buffer sizes) only.
-# Linked frames with at least this many blocks on average, in a batch of few
-# linked frames, compress speculatively (a wavefront per block); otherwise one
-# wavefront per frame, which is parallel over the frames
-_BATCH_SPEC_MAX_FRAMES = 256
 
 
 def _on(stream):
@@ -928,21 +939,6 @@ def _spans(buf, off, length, what):
     return off, length, total
 
 
-def _launch_subset(mask, arrays, out_len, launch):
-    """launch(*arrays restricted to the blocks of `mask`, out, count); the blocks' results go to out_len."""
-    nb = mask.numel()
-    sel = torch.nonzero(mask).flatten()
-    m = sel.numel()
-    if m == 0:
-        return
-    if m == nb:
-        launch(*arrays, out_len, nb)
-        return
-    out = torch.empty(m, dtype=torch.int32, device=mask.device)
-    launch(*(a[sel] for a in arrays), out, m)
-    out_len[sel] = out
-
-
 def compress_batch(src, src_off, src_len, *, compression_level=0, block_size=0, content_checksum=False,
                    block_checksum=False, block_linked=True, store_size=True, parse="exact", stream=None):
     """compress_device for n inputs in one call: input i is
@@ -962,8 +958,7 @@ def compress_batch(src, src_off, src_len, *, compression_level=0, block_size=0, 
     inputs straddle the block size uses both.  Content checksums are hashed
     on the device, four lanes per frame (lz4m_xxh32_batch): a very large frame
     in a batch hashes serially; that is what the single-frame calls are for."""
-    level, accel = _parse_level(parse, compression_level)
-    _no_linked_optimal(parse, block_linked)
+    p = resolve_parse(parse, compression_level, block_linked)
     req = max(-1, min(int(block_size), 8))   # beyond 7 it is no block size whatever the input's length
     with _on(stream):
         off, ln, src_total = _spans(src, src_off, src_len, "src")
@@ -986,8 +981,12 @@ def compress_batch(src, src_off, src_len, *, compression_level=0, block_size=0, 
             cmp_off = N.exclusive_scan(P["slot_len"])
             cmp = torch.empty(src_total + src_total // 255 + 17 * nb + 64, dtype=torch.uint8, device=dev)
             cmp_len = torch.zeros(nb, dtype=torch.int32, device=dev)
-            _compress_blocks(src, P, cmp, cmp_off[:nb].contiguous(), cmp_len, parse, level, accel,
-                             bsid, linked, _BLOCK_SIZES[top], n_linked)
+            # the per-block masks, where the parse splits by them and the plan is not uniform
+            owner = P["owner"]
+            in_linked = linked[owner] != 0 if n_linked and p.history else False
+            big = bsid[owner] > BLOCKSIZE_MAX64KB if top > BLOCKSIZE_MAX64KB and p.table == N.PARSE_PARALLEL else False
+            _compress_blocks(src, P, cmp, cmp_off[:nb].contiguous(), cmp_len, p, in_linked, big, _BLOCK_SIZES[top],
+                             n_linked)
             rec_len = torch.empty(nb, dtype=torch.int32, device=dev)
             N.frame_block_sizes(P["raw_len"], cmp_len, block_checksum, rec_len, nb)
             rec_off = N.exclusive_scan(rec_len)
@@ -1007,57 +1006,40 @@ def compress_batch(src, src_off, src_len, *, compression_level=0, block_size=0, 
         return frames[:total], frame_off, fsize
 
 
-def _compress_blocks(src, P, cmp, cmp_off, cmp_len, parse, level, accel, bsid, linked, max_block, n_linked):
-    """Compress the planned blocks of all frames into their slots of `cmp`:
-    two launches' worth of groups, picked by a per-block mask."""
-    arrays = (P["raw_off"], P["raw_len"], cmp_off, P["cap"])
+def _compress_blocks(src, P, cmp, cmp_off, cmp_len, p, linked, big, max_len, n_linked, stream=None):
+    """The block stage of every frame compression: the planned blocks (P: frames_plan_blocks' arrays or
+    _plan_one's) into their slots of `cmp` with the parse ``p``, in at most two launches picked per block.
+    ``linked``: the block's frame is linked; ``big``: its blocks are above 64 KiB -- a bool where the host knows
+    one answer for all blocks (a single frame; a batch whose plan found none: no read-back), else a mask (one
+    read-back each way).  ``max_len`` bounds the longest block; ``n_linked`` counts the linked frames."""
+    if p.launcher == "table" and p.table == N.PARSE_PARALLEL:  # by block size: the large-block launch above 64 KiB
+        groups = [(p, big, False), (p._replace(table=N.PARSE_PARALLEL_LARGE), big, True)]
+    elif p.history:                                            # by linking: P[p.history] goes with a linked frame's blocks
+        groups = [(p._replace(history=""), linked, False), (p, linked, True)]
+    else:
+        groups = [(p, False, False)]
+    arrays = (P["raw_off"], P["raw_len"], cmp_off, P["cap"], P.get(p.history))
     nb = cmp_len.numel()
-    if parse == "parallel":
-        def small(o, ln, co, cap, out, m):
-            N.launch_compress(src, o, ln, cmp, co, cap, out, m, N.PARSE_PARALLEL, accel)
-
-        def large(o, ln, co, cap, out, m):
-            N.launch_compress(src, o, ln, cmp, co, cap, out, m, N.PARSE_PARALLEL_LARGE, accel, max_len=max_block)
-
-        if max_block <= 65536:                                 # one kind only: no split, no read-back
-            small(*arrays, cmp_len, nb)
-            return
-        big = bsid[P["owner"]] > BLOCKSIZE_MAX64KB
-        _launch_subset(~big, arrays, cmp_len, small)
-        _launch_subset(big, arrays, cmp_len, large)
-        return
-    if parse == "optimal":                                     # independent blocks only
-        N.launch_compress_opt(src, P["raw_off"], P["raw_len"], cmp, cmp_off, P["cap"], cmp_len, nb, level,
-                              max_len=max_block)
-        return
-    in_linked = linked[P["owner"]] != 0 if n_linked else None
-    if parse == "hc":
-        def indep(o, ln, co, cap, out, m):
-            N.launch_compress_hc(src, o, ln, cmp, co, cap, out, m, level, max_len=max_block)
-
-        def chained(o, ln, co, cap, hist, out, m):
-            N.launch_compress_hc(src, o, ln, cmp, co, cap, out, m, level, max_len=max_block, dict_len=hist)
-
-        if in_linked is None:
-            indep(*arrays, cmp_len, nb)
-            return
-        _launch_subset(~in_linked, arrays, cmp_len, indep)
-        _launch_subset(in_linked, arrays + (P["hist"],), cmp_len, chained)
-        return
-
-    def indep(o, ln, co, cap, out, m):                         # lz4frame.c:853-863
-        N.launch_compress(src, o, ln, cmp, co, cap, out, m, N.TABLE_AUTO, accel)
-
-    def chained(o, ln, co, cap, link, out, m):                 # lz4frame.c:865-871
+    for q, mask, want in groups:
+        sel = None                                             # the blocks where the mask says `want`; None: all
+        if isinstance(mask, bool):
+            if mask != want:
+                continue
+        else:
+            sel = torch.nonzero(mask if want else ~mask).flatten()
+            if sel.numel() == 0:
+                continue
+            if sel.numel() == nb:
+                sel = None
+        o, ln, co, cap, extra = arrays if sel is None else (a if a is None else a[sel] for a in arrays)
+        m = nb if sel is None else sel.numel()
+        out = cmp_len if sel is None else torch.empty(m, dtype=torch.int32, device=cmp_len.device)
+        # few linked frames of at least _SPEC_MIN_BLOCKS blocks on average: speculatively, a wavefront per block
         spec = n_linked < _BATCH_SPEC_MAX_FRAMES and m >= _SPEC_MIN_BLOCKS * n_linked
-        N.launch_compress_linked(src, o, ln, link, cmp, co, cap, out, m, accel,
-                                 mode=N.LINKED_SPECULATIVE if spec else N.LINKED_SERIAL)
-
-    if in_linked is None:
-        indep(*arrays, cmp_len, nb)
-        return
-    _launch_subset(~in_linked, arrays, cmp_len, indep)
-    _launch_subset(in_linked, arrays + (P["link"],), cmp_len, chained)
+        N.launch_blocks(q, src, o, ln, cmp, co, cap, out, m, extra=extra if q.history else None, max_len=max_len,
+                        speculative=spec, stream=stream)
+        if sel is not None:
+            cmp_len[sel] = out
 
 
 def decompress_batch(frames, frame_off, frame_len, *, stream=None):
@@ -1176,7 +1158,7 @@ def compress_many(datas, compression_level=0, block_size=0, content_checksum=Fal
         return [compress(v, level, bsid_req, content_checksum, block_checksum, block_linked, store_size,
                          return_bytearray) for v in views]
     N.device()
-    _parse_level("exact", level)
+    resolve_parse("exact", level, block_linked)
     buf, d_off, d_len = _stage_many(views)
     frames, f_off, f_len = compress_batch(buf, d_off, d_len, compression_level=level, block_size=bsid_req,
                                           content_checksum=content_checksum, block_checksum=block_checksum,

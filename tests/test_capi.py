@@ -97,8 +97,8 @@ def test_argument_validation_without_gpu():
     for dec in N.DECODERS.values():
         assert lib.lz4m_decompress_batch_sel(None, None, None, None, None, None, None, 0, None, 0, dec, None) == 0
     assert lib.lz4m_xxh32_long(None, -1, 0, None, None) == N.EINVAL
-    assert lib.lz4m_frame_scan(None, -1, 0, 0, 0, 65536, 1, None, None, None, None, None) == N.EINVAL
-    assert lib.lz4m_frame_scan(None, 16, 0, 0, 0, 65536, 1, None, None, None, None, None) == N.EINVAL
+    assert lib.lz4m_frame_scan(None, -1, 0, 0, 0, 65536, 1, None, None, None, None, None, None) == N.EINVAL
+    assert lib.lz4m_frame_scan(None, 16, 0, 0, 0, 65536, 1, None, None, None, None, None, None) == N.EINVAL
     # host single-buffer functions reject bad sizes before touching a device
     assert lib.lz4m_decompress_safe(None, None, -1, 10) == -1
     assert lib.lz4m_compress_default(None, None, -1, 10) == 0
