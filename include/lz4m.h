@@ -331,6 +331,36 @@ int lz4m_decompress_batch_sel(const uint8_t* d_src, const int64_t* d_src_off, co
                               lz4m_stream_t stream);
 
 /*
+ * Decoded sizes without decoding (lz4m_sizes.hip): d_size[i] = the value
+ * LZ4_decompress_safe(block i, dst, d_src_len[i], cap) returns once cap is
+ * large enough not to matter (any cap >= 255 * d_src_len[i] + 64 gives it),
+ * or, with d_dict_len (NULL: no dictionaries), the value
+ * LZ4_decompress_safe_usingDict returns with d_dict_len[i] bytes of
+ * dictionary: the decoded size, or -(error position) - 1 with the
+ * reference's error position.  The walk makes every test the decoders make
+ * except the capacity tests: a match offset beyond the output so far plus a
+ * dictionary below 64 KiB fails; offset 0 does not, as in the decoders.  A
+ * size above INT32_MAX reports LZ4M_SIZE_OVERFLOW; d_src_len[i] <= 0 reports
+ * -1.  A block decoded with exactly this capacity can still fail: the
+ * reference wants 12 bytes of output after the start of the last match and 5
+ * after its end (lz4.c:2296, :2312), which blocks of conformant compressors
+ * have.  Reads the compressed bytes once and writes 4 bytes per block.
+ * walk: LZ4M_WALK_LANE, one lane per block (large batches); LZ4M_WALK_WAVE,
+ * one wavefront per block (few or large blocks); LZ4M_WALK_AUTO, the lane
+ * walk from 24 576 blocks (the measured crossover with 64 KiB blocks).  Both
+ * give the same values.  One launch,
+ * stream-ordered, no allocation, no scratch, no synchronisation.
+ * LZ4M_EINVAL, before any HIP call: n < 0 or an unknown walk; n == 0 returns 0.
+ */
+#define LZ4M_SIZE_OVERFLOW INT32_MIN
+#define LZ4M_WALK_AUTO 0   /* by batch size */
+#define LZ4M_WALK_LANE 1
+#define LZ4M_WALK_WAVE 2
+int lz4m_decompressed_size_batch(const uint8_t* d_src, const int64_t* d_src_off, const int32_t* d_src_len,
+                                 const int32_t* d_dict_len /* NULL: none */, int32_t* d_size, int64_t n,
+                                 int walk, lz4m_stream_t stream);
+
+/*
  * Batched LZ4_decompress_safe_usingDict with the dictionary in a separate
  * buffer (usingExtDict, lz4.c:2612-2625, the `dict=` argument of
  * lz4.block.decompress, _block.c:357-359).  Dictionary i is

@@ -270,6 +270,50 @@ __device__ __forceinline__ int32_t div255(int32_t y) {
 template <bool BIG>
 __device__ __forceinline__ int32_t ext_len(int32_t x) { return x >= 15 ? 1 + div255<BIG>(x - 15) : 0; }
 
+// read_variable_length (lz4.c:1903-1928) over a stream read 16 bytes at a
+// time: in16(p) = the 16 stream bytes at p, with bytes at or beyond the
+// block's end read as zero.  On failure ip is the position the reference
+// reports.
+template <typename In16>
+__device__ __forceinline__ bool len_run(In16&& in16, int64_t& ip, int64_t ilimit, bool initial_check, int64_t& out) {
+    if (initial_check && ip >= ilimit) return false;
+    // 16 bytes per load: a run of 255s (a long literal or match, e.g. the
+    // 257 length bytes of a stored-looking 64 KiB block) costs one memory
+    // round trip per 16 bytes instead of per byte.  Same outcome as the
+    // reference's byte loop: reading the byte at ilimit fails with
+    // ip = ilimit + 1 (ilimit < iend, so every byte up to it is readable;
+    // in16 zero-fills past iend, i.e. past ilimit).
+    if (ip >= ilimit) {   // the first byte read already fails (ip + 1)
+        ++ip;
+        return false;
+    }
+    int64_t len = 0;
+    for (;;) {
+        const u32x4 v = in16(ip);
+        const uint32_t n0 = ~v.x, n1 = ~v.y, n2 = ~v.z, n3 = ~v.w;
+        const uint32_t q = n0 ? 0u : n1 ? 1u : n2 ? 2u : n3 ? 3u : 4u;
+        if (q < 4) {
+            const uint32_t nw = q == 0 ? n0 : q == 1 ? n1 : q == 2 ? n2 : n3;
+            const uint32_t bi = (uint32_t)__builtin_ctz(nw) >> 3;
+            const uint32_t j = 4 * q + bi;   // first byte != 255
+            if (ip + (int64_t)j >= ilimit) {
+                ip = ilimit + 1;
+                return false;
+            }
+            len += 255 * (int64_t)j + (int64_t)((~nw >> (8 * bi)) & 0xFFu);   // no indexed access: no scratch
+            ip += j + 1;
+            out = len;
+            return true;
+        }
+        if (ip + 16 > ilimit) {   // the run reaches ilimit
+            ip = ilimit + 1;
+            return false;
+        }
+        len += 255 * 16;
+        ip += 16;
+    }
+}
+
 // ------------------------------------------------------------ exact puts
 // Store exactly k (0..16) bytes of v at global address p (any alignment).
 __device__ __forceinline__ void put_exact(uint8_t* p, u32x4 v, uint32_t k) {

@@ -31,6 +31,9 @@ LINKED_SPECULATIVE = 2
 EINVAL = 0x10000
 # decoder selector of lz4m_decompress_batch_sel (include/lz4m.h)
 DECODERS = {"auto": 0, "hist": 3, "rows": 4}
+# walk selector of lz4m_decompressed_size_batch, and its status for a size above INT32_MAX
+WALKS = {"auto": 0, "lane": 1, "wave": 2}
+SIZE_OVERFLOW = -(2**31)
 
 _lock = threading.Lock()
 _lib = None
@@ -50,6 +53,7 @@ def _declare(lib) -> None:
         "lz4m_decompress_batch_sel": ([vp, vp, vp, vp, vp, vp, vp, i64, vp, C.c_size_t, i32, vp], i32),
         "lz4m_decompress_batch_dict": ([vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp], i32),
         "lz4m_decompress_batch_prefix": ([vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp], i32),
+        "lz4m_decompressed_size_batch": ([vp, vp, vp, vp, vp, i64, i32, vp], i32),
         "lz4m_decompress_chain": ([vp, vp, vp, vp, vp, vp, i64, i32, vp], i32),
         "lz4m_compress_batch": ([vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, vp], i32),
         "lz4m_compress_dict_batch": ([vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, vp], i32),
@@ -177,6 +181,18 @@ def launch_decompress(src, src_off, src_len, dst, dst_off, dst_cap, status, n, s
                                           ptr(dst_cap), ptr(dict_buf), ptr(dict_off), ptr(dict_len), ptr(status),
                                           n, sp)
     check(rc, "lz4m_decompress_batch")
+
+
+def launch_decompressed_size(src, src_off, src_len, size, n, stream=None, dict_len=None, walk: str = "auto") -> None:
+    """Decoded sizes without decoding (lz4m_decompressed_size_batch): size[i]
+    = what the decoders report for block i at a capacity large enough not to
+    matter, with ``dict_len`` (int32[n] or None) bytes of dictionary.
+    ``walk``: a key of ``WALKS``."""
+    if walk not in WALKS:
+        raise ValueError(f"walk must be one of {sorted(WALKS)}, not {walk!r}")
+    check(lib().lz4m_decompressed_size_batch(ptr(src), ptr(src_off), ptr(src_len), ptr(dict_len), ptr(size), n,
+                                             WALKS[walk], stream_ptr(stream)),
+          "lz4m_decompressed_size_batch")
 
 
 _WORK: "collections.OrderedDict" = collections.OrderedDict()

@@ -5,6 +5,8 @@ from ._block import (  # noqa: F401  batched / device-resident extensions
     decompress_many,
     compress_batch,
     decompress_batch,
+    decompressed_size_batch,
+    decompressed_size_many,
     decompress_host,
     compact,
     xxh32_batch,

@@ -496,22 +496,60 @@ def compress_many(blocks, accel: int = 1, store_size: bool = True, as_bytearray:
     return res
 
 
+def _restage_caps(dev, lay: _Layout, h, d, n: int, d_off, caps):
+    """A staged batch whose capacities are known only now: the layout with
+    an output region of sum(caps) bytes, the staged tables and payload kept
+    on the device (moved when the buffer has to grow) and the two output
+    tables written again.  Returns (layout, host, device)."""
+    lay2 = _Layout(n, lay.h2d - lay.payload, sum(caps))
+    h2, d2 = _stage(dev, lay2.total, lay2.total)
+    if d2 is not d:
+        d2[:lay.h2d].copy_(d[:lay.h2d])
+    hn = h2.numpy()
+    hn[lay2.dst_off:lay2.dst_off + 8 * n].view(np.int64)[:] = d_off
+    hn[lay2.dst_cap:lay2.dst_cap + 4 * n].view(np.int32)[:] = caps
+    d2[lay2.dst_off:lay2.payload].copy_(h2[lay2.dst_off:lay2.payload], non_blocking=True)
+    return lay2, h2, d2
+
+
+def _dict_args(dict, n: int, dev):
+    """(device dictionary, its offsets, its lengths) shared by n blocks, or
+    three Nones without a dictionary (an empty one is none)."""
+    if dict is None or not _buffer(dict).nbytes:
+        return None, None, None
+    dv = _buffer(dict)
+    return (N.to_device(dv, dev), torch.zeros(n, dtype=torch.int64, device=dev),
+            torch.full((n,), dv.nbytes, dtype=torch.int32, device=dev))
+
+
 def decompress_many(blocks, uncompressed_size=-1, dict=None, as_bytearray: bool = False,
                     raise_errors: bool = True):
     """Decompress a sequence of host buffers in one launch.
 
-    ``uncompressed_size`` is one int for all blocks or a list; negative
-    means "read the LE32 size header".  With ``raise_errors`` the first
-    failing block raises the reference's exception; otherwise failing blocks
-    yield the LZ4BlockError instance in their slot.
+    ``uncompressed_size`` is one value for all blocks or a list: an int >= 0
+    is the block's capacity, a negative int means "read the LE32 size
+    header", and ``None`` means "no size header and the size is unknown"
+    (``compress(store_size=False)`` output, raw ``LZ4_compress_*`` output).
+    For the ``None`` blocks the staged sources first go through the decoded-
+    size pass (``decompressed_size_batch``, with ``dict``'s length), one
+    read-back of the sizes lays the output out, and each decodes at exactly
+    its size (see ``decompress_batch`` for what that capacity means).  With
+    ``raise_errors`` the first failing block raises the reference's
+    exception; otherwise failing blocks yield the LZ4BlockError instance in
+    their slot.
     """
     views = [_buffer(b) for b in blocks]
     n = len(views)
     if n == 0:
         return []
     sizes = list(uncompressed_size) if isinstance(uncompressed_size, (list, tuple)) else [uncompressed_size] * n
+    unknown = [us is None for us in sizes]
     caps, skip, errors = [], [], [None] * n
     for i, (v, us) in enumerate(zip(views, sizes)):
+        if us is None:   # capacity from the size pass, below
+            caps.append(0)
+            skip.append(0)
+            continue
         try:
             cap, sk = _cap_and_skip(v, us)
         except ValueError as err:
@@ -520,24 +558,34 @@ def decompress_many(blocks, uncompressed_size=-1, dict=None, as_bytearray: bool 
             errors[i], cap, sk = err, 0, 0   # decoded as an empty block, reported in its slot
         caps.append(cap)
         skip.append(sk)
+    from_header = [us is not None and us < 0 for us in sizes]
     dev = N.device()
     lens = [v.nbytes for v in views]
     offs = _excl_offsets(lens)
     d_off = _excl_offsets(caps)
     lay, h, d = _stage_in(dev, views, offs, lens, d_off, caps, skip=skip)
+    d_dict, dict_off, dict_len = _dict_args(dict, n, dev)
+    passed = None
+    if any(unknown):
+        d_src, src_off, src_len = _dev_views(lay, d, n)[:3]
+        size = torch.empty(n, dtype=torch.int32, device=dev)
+        N.launch_decompressed_size(d_src, src_off, src_len, size, n, dict_len=dict_len)
+        passed = size.tolist()   # the one read-back that lays the output out
+        caps = [max(p, 0) if u else c for p, u, c in zip(passed, unknown, caps)]
+        d_off = _excl_offsets(caps)
+        lay, h, d = _restage_caps(dev, lay, h, d, n, d_off, caps)
     d_src, src_off, src_len, d_dst, dst_off, dst_cap, status = _dev_views(lay, d, n)
-    if dict is not None and _buffer(dict).nbytes:
-        dv = _buffer(dict)
-        d_dict = N.to_device(dv, dev)
+    if d_dict is not None:
         N.launch_decompress(d_src, src_off, src_len, d_dst, dst_off, dst_cap, status, n,
-                            dict_buf=d_dict, dict_off=torch.zeros(n, dtype=torch.int64, device=dev),
-                            dict_len=torch.full((n,), dv.nbytes, dtype=torch.int32, device=dev))
+                            dict_buf=d_dict, dict_off=dict_off, dict_len=dict_len)
     else:
         N.launch_decompress(d_src, src_off, src_len, d_dst, dst_off, dst_cap, status, n,
                             src_bytes=int(sum(lens)))
     st, host = _stage_out(lay, h, d, n)
+    if passed is not None:   # a block the size pass rejected keeps that status
+        st = [p if u and p < 0 else r for r, p, u in zip(st, passed, unknown)]
     if n >= _MANY and all(e is None for e in errors) and all(
-            r >= 0 and (r == c or us >= 0) for r, c, us in zip(st, caps, sizes)) and sum(st) >= _MANY_BYTES:
+            r >= 0 and (r == c or not fh) for r, c, fh in zip(st, caps, from_header)) and sum(st) >= _MANY_BYTES:
         return _results_many(host, d_off, st, None, as_bytearray)   # every block decoded as asked
     res = []
     for i in range(n):
@@ -545,7 +593,7 @@ def decompress_many(blocks, uncompressed_size=-1, dict=None, as_bytearray: bool 
             res.append(errors[i])
             continue
         r = st[i]
-        err = _decode_error(r, caps[i], sizes[i] < 0)
+        err = _decode_error(r, caps[i], from_header[i])
         if err is not None:
             if raise_errors:
                 raise err
@@ -555,6 +603,33 @@ def decompress_many(blocks, uncompressed_size=-1, dict=None, as_bytearray: bool 
         body = host[o:o + r].tobytes() if r else b""
         res.append(bytearray(body) if as_bytearray else body)
     return res
+
+
+def decompressed_size_many(blocks, dict=None, raise_errors: bool = True):
+    """The decoded size of each host buffer (a block without a size header),
+    without decoding it: ``decompressed_size_batch`` on the staged blocks,
+    with ``dict``'s length as every block's dictionary length.  A block the
+    pass rejects raises ``LZ4BlockError`` ("Decompression failed ..."); with
+    ``raise_errors=False`` its negative status stays in the list."""
+    views = [_buffer(b) for b in blocks]
+    n = len(views)
+    if n == 0:
+        return []
+    dev = N.device()
+    lens = [v.nbytes for v in views]
+    zeros = [0] * n
+    lay, _h, d = _stage_in(dev, views, _excl_offsets(lens), lens, zeros, zeros)
+    d_src, src_off, src_len = _dev_views(lay, d, n)[:3]
+    nd = 0 if dict is None else _buffer(dict).nbytes
+    dict_len = torch.full((n,), nd, dtype=torch.int32, device=dev) if nd else None
+    size = torch.empty(n, dtype=torch.int32, device=dev)
+    N.launch_decompressed_size(d_src, src_off, src_len, size, n, dict_len=dict_len)
+    out = size.tolist()
+    if raise_errors:
+        for r in out:
+            if r < 0:
+                raise _decode_error(r, 0, False)
+    return out
 
 
 # ------------------------------------------------- device-resident batches
@@ -621,7 +696,28 @@ def compress_batch(src: torch.Tensor, src_off: torch.Tensor, src_len: torch.Tens
     return dst, dst_off, out_len
 
 
-def decompress_batch(src: torch.Tensor, src_off: torch.Tensor, src_len: torch.Tensor, dst_cap: torch.Tensor, *,
+def decompressed_size_batch(src: torch.Tensor, src_off: torch.Tensor, src_len: torch.Tensor, *,
+                            dict_len: torch.Tensor | None = None, walk: str = "auto", stream=None):
+    """The decoded sizes of n device-resident blocks without decoding them,
+    one stream-ordered launch (lz4m_decompressed_size_batch), no host
+    synchronisation.  Returns int32[n]: what ``decompress_batch`` reports for
+    block i at a capacity large enough not to matter (any capacity of at
+    least 255 * src_len[i] + 64 gives it) -- the decoded size, or -(pos)-1
+    with the reference's error position.  ``dict_len`` int32[n]: the length of
+    each block's dictionary (matches may reach that far before the block;
+    only the length counts).  A size above 2**31 - 1 reports -2**31.
+    ``walk``: "lane" (a lane per block, large batches), "wave" (a wavefront
+    per block, few or large blocks) or "auto" (by batch size); all give the
+    same values.  Validates a batch of untrusted blocks for everything but
+    the bytes a match copies."""
+    n = src_off.numel()
+    size = torch.empty(n, dtype=torch.int32, device=src.device)
+    N.launch_decompressed_size(src, src_off, src_len, size, n, stream, dict_len, walk)
+    return size
+
+
+def decompress_batch(src: torch.Tensor, src_off: torch.Tensor, src_len: torch.Tensor,
+                     dst_cap: torch.Tensor | None = None, *,
                      dst: torch.Tensor | None = None, dst_off: torch.Tensor | None = None,
                      dict_buf: torch.Tensor | None = None, dict_off: torch.Tensor | None = None,
                      dict_len: torch.Tensor | None = None, stream=None):
@@ -629,9 +725,28 @@ def decompress_batch(src: torch.Tensor, src_off: torch.Tensor, src_len: torch.Te
 
     Returns (dst, dst_off, status): status int32[n] is the decoded size or
     -(pos)-1 exactly as LZ4_decompress_safe(_usingDict) would return.
+
+    ``dst_cap=None``: the sizes are not known.  They come from the decoded-
+    size pass (``decompressed_size_batch``, with ``dict_len`` when a
+    dictionary is given): dst_cap = size.clamp(min=0), ``dst_off`` its
+    exclusive scan, and the output is exactly packed (one read-back for the
+    total, as ``dst=None`` always costs).  ``status`` is what the decode
+    returns at that capacity:
+      - a block that decodes only with slack fails here: one whose last match
+        starts within 12 bytes of the end of the output or ends within 5
+        (lz4.c:2296, :2312).  No conformant compressor writes such blocks, and
+        the reference fails at the same capacity;
+      - a block whose size pass failed has capacity 0 and keeps the size
+        pass's negative status.
     """
     n = src_off.numel()
     dev = src.device
+    passed = None
+    if dst_cap is None:
+        passed = decompressed_size_batch(src, src_off, src_len, dict_len=None if dict_buf is None else dict_len,
+                                         stream=stream)
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(dev)):
+            dst_cap = passed.clamp(min=0)
     if dst_off is None:
         dst_off = N.exclusive_scan(dst_cap, stream=stream)[:n]
     if dst is None:
@@ -640,6 +755,9 @@ def decompress_batch(src: torch.Tensor, src_off: torch.Tensor, src_len: torch.Te
     status = torch.empty(n, dtype=torch.int32, device=dev)
     N.launch_decompress(src, src_off, src_len, dst, dst_off, dst_cap, status, n, stream,
                         dict_buf, dict_off, dict_len)
+    if passed is not None:
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(dev)):
+            status = torch.where(passed < 0, passed, status)
     return dst, dst_off, status
 
 

@@ -1042,7 +1042,7 @@ def _compress_blocks(src, P, cmp, cmp_off, cmp_len, p, linked, big, max_len, n_l
             cmp_len[sel] = out
 
 
-def decompress_batch(frames, frame_off, frame_len, *, stream=None):
+def decompress_batch(frames, frame_off, frame_len, *, stream=None, direct: bool = False):
     """decompress_device for n frames in one call: frame i is the
     frame_len[i] bytes at frames[frame_off[i]] of a uint8 device tensor
     (bytes after a frame's end are allowed).  Returns (out, out_off, out_len,
@@ -1061,7 +1061,22 @@ def decompress_batch(frames, frame_off, frame_len, *, stream=None):
     (lz4m_decompress_chains); one gather packs the blocks of every frame
     back to back (a block may decode short of the block size) and takes stored
     blocks from the frame.  Checksums are verified on the device; the content
-    hash is four lanes per frame."""
+    hash is four lanes per frame.
+
+    ``direct=True``: the compressed blocks of frames that are not chains
+    (chains: linked frames of more than one block) are sized first
+    (lz4m_decompressed_size_batch) and decode straight into ``out`` at their
+    final positions with their size as capacity: no slots for these frames
+    and no second copy of their bytes.  Chains keep the slots, for their
+    frames only (their kernel gives every block the frame's block size as
+    capacity, and its wild stores would reach the next frame's bytes in a
+    packed buffer).  For frames written by any compressor of this package or
+    the reference the five tensors are those of ``direct=False``.  One
+    difference: a block that decodes only with slack (its last match starts
+    within 12 bytes of the block's end or ends within 5; no conformant
+    compressor writes one) fails at its exact size, so a frame holding one
+    has status LZ4M_FRAME_BLOCK_FAILED here where ``direct=False`` reports
+    what the rest of the frame gives (0 without a content checksum)."""
     with _on(stream):
         off, ln, _ = _spans(frames, frame_off, frame_len, "frames")
         dev = frames.device
@@ -1075,6 +1090,9 @@ def decompress_batch(frames, frame_off, frame_len, *, stream=None):
         flags = S["flags"]
         maxb = torch.ones_like(S["content_size"]) << (8 + 2 * S["bsid"].to(torch.int64))
         fcap = S["nblocks"].to(torch.int64) * maxb
+        chain = ((flags & N.FRAME_LINKED) != 0) & (S["nblocks"] > 1)   # lz4frame.c:1853-1856
+        if direct:   # slots for the chains only
+            fcap = torch.where(chain, fcap, torch.zeros_like(fcap))
         slot_end = torch.cumsum(fcap, 0)
         slot_base = slot_end - fcap
         nb, slot_total, any_bc, any_cc = torch.stack([
@@ -1084,28 +1102,47 @@ def decompress_batch(frames, frame_off, frame_len, *, stream=None):
         if nb:
             R = N.frames_records(frames, off, ln, S, base, slot_base, n, nb)
             owner = R["frame"]
-            chain = ((flags & N.FRAME_LINKED) != 0) & (S["nblocks"] > 1)   # lz4frame.c:1853-1856
             in_chain = chain[owner]
             stored = (R["raw"] != 0) & ~in_chain
             slots = torch.empty(slot_total + 16, dtype=torch.uint8, device=dev)
             blk = torch.empty(nb, dtype=torch.int32, device=dev)
             # stored blocks and the chains' blocks go to the decoder with length 0 (rejected at once, no work)
-            dec_len = torch.where(stored | in_chain, torch.zeros_like(R["len"]), R["len"])
-            N.launch_decompress(frames, R["pos"], dec_len, slots, R["slot_off"], R["slot_cap"], blk, nb)
+            zlen = torch.zeros_like(R["len"])
+            dec_len = torch.where(stored | in_chain, zlen, R["len"])
             count = torch.where(chain, S["nblocks"], torch.zeros_like(S["nblocks"]))
-            N.launch_decompress_chains(frames, R["pos"], R["len"], R["raw"], base, count, slots, slot_base,
-                                       maxb.to(torch.int32), blk, n)
-            size = torch.where(stored, R["len"], blk.clamp(min=0))
-            bad = ((blk < 0) & ~stored).to(torch.int32)
+            if direct:
+                # a block's size, as the frame's decoder would find it: at most the frame's block size
+                # (lz4frame.c:1844-1847), else the block fails
+                sized = torch.empty(nb, dtype=torch.int32, device=dev)
+                N.launch_decompressed_size(frames, R["pos"], dec_len, sized, nb)
+                fits = (sized >= 0) & (sized <= R["slot_cap"])
+                N.launch_decompress_chains(frames, R["pos"], R["len"], R["raw"], base, count, slots, slot_base,
+                                           maxb.to(torch.int32), blk, n)
+                size = torch.where(stored, R["len"],
+                                   torch.where(in_chain, blk.clamp(min=0), torch.where(fits, sized, zlen)))
+            else:
+                N.launch_decompress(frames, R["pos"], dec_len, slots, R["slot_off"], R["slot_cap"], blk, nb)
+                N.launch_decompress_chains(frames, R["pos"], R["len"], R["raw"], base, count, slots, slot_base,
+                                           maxb.to(torch.int32), blk, n)
+                size = torch.where(stored, R["len"], blk.clamp(min=0))
             goff = N.exclusive_scan(size)
             out_off = goff[base[:-1]]
             out_len = goff[base[1:]] - out_off
             out_total = int(goff[-1])
             out = torch.empty(out_total + 16, dtype=torch.uint8, device=dev)
-            # a chain wrote its blocks back to back from its frame's first slot
-            from_slot = torch.where(in_chain, slot_base[owner] + (goff[:nb] - out_off[owner]), R["slot_off"])
             zero = torch.zeros_like(size)
-            N.gather(slots, from_slot, torch.where(stored, zero, size), out, goff, nb)
+            if direct:
+                here = torch.empty(nb, dtype=torch.int32, device=dev)
+                N.launch_decompress(frames, R["pos"], torch.where(fits, dec_len, zlen), out, goff,
+                                    torch.where(in_chain | stored, zero, size), here, nb)
+                blk = torch.where(in_chain, blk, here)
+                from_slot = slot_base[owner] + (goff[:nb] - out_off[owner])
+                N.gather(slots, from_slot, torch.where(in_chain, size, zero), out, goff, nb)
+            else:
+                # a chain wrote its blocks back to back from its frame's first slot
+                from_slot = torch.where(in_chain, slot_base[owner] + (goff[:nb] - out_off[owner]), R["slot_off"])
+                N.gather(slots, from_slot, torch.where(stored, zero, size), out, goff, nb)
+            bad = ((blk < 0) & ~stored).to(torch.int32)
             N.gather(frames, R["pos"], torch.where(stored, size, zero), out, goff, nb)
             fbad = torch.zeros(n, dtype=torch.int32, device=dev).index_add_(0, owner, bad)
             status = torch.where((status == 0) & (fbad > 0), torch.full_like(status, N.FRAME_BLOCK_FAILED), status)
@@ -1173,17 +1210,17 @@ def _unpack_many(buf, off, length, as_bytearray):
     return B._results_many(host, off.cpu().tolist(), length.cpu().tolist(), None, as_bytearray)
 
 
-def decompress_many(frames, return_bytearray=False, return_bytes_read=False):
+def decompress_many(frames, return_bytearray=False, return_bytes_read=False, direct: bool = False):
     """[decompress(f, ...) for f in frames] in one batched call
-    (decompress_batch).  If a frame fails, the lowest failing index raises
-    what ``decompress`` raises for its bytes."""
+    (decompress_batch; ``direct`` as there).  If a frame fails, the lowest
+    failing index raises what ``decompress`` raises for its bytes."""
     views = [_buffer(f, "data") for f in frames]
     if not views:
         return []
     if max(v.nbytes for v in views) > 0x7FFFFFFF:
         return [decompress(v, return_bytearray, return_bytes_read) for v in views]
     buf, d_off, d_len = _stage_many(views)
-    out, o_off, o_len, status, read = decompress_batch(buf, d_off, d_len)
+    out, o_off, o_len, status, read = decompress_batch(buf, d_off, d_len, direct=direct)
     st = status.cpu().tolist()
     for i, s in enumerate(st):
         if s != 0:
